@@ -12,6 +12,10 @@ SineGen noise) are resident in HBM before the timed region; the request block it
 utterances) travels inside the step because that IS the first message of the sharded step (mlx_audio_amd/shard.py: rank 0
 owns the request queue; one broadcast).  ``--config whisper | qwen3 | csm`` run the secondary lines with the same schema.
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.  ``--full`` adds the legs that are not the headline figure: the
+batch-vs-single check, the precision-2 leg, the roofline (instrumented step + in-run PMC passes), the one-utterance latency and the CPU baseline.
+``--dump-outputs DIR`` writes the waveforms of the last timed step as .npy files (see ``dump_outputs``).
+
 Rank 0 prints ONE JSON line; see DESIGN.md section "Measurement" for every field.
 """
 import argparse
@@ -44,8 +48,13 @@ def parse():
                     help="default: the mode load_model() / KokoroEngine pick for a bf16 checkpoint (KokoroEngine.default_precision = 6: vocoder convs of >= 7 taps\n"
                          "as fp16 hi pass + block-scaled FP4 lo pass; parity at the benchmarked batch: tests/test_kokoro_gpu.py::\n"
                          "test_kokoro_default_mode_batch64_canonical).  5 = the e4m3 lo pass of rounds 4 - 5 (7.9e-5 of the peak), 2 = bf16 hi+lo split MFMA\n"
-                         "everywhere (3e-5), 3 = single fp16 pass in the vocoder (misses the 2e-3 bar), 1 = single bf16 pass.  The default run also reports\n"
+                         "everywhere (3e-5), 3 = single fp16 pass in the vocoder (misses the 2e-3 bar), 1 = single bf16 pass.  A --full run also reports\n"
                          "mode 2 as value_precision2")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: batch_vs_single, value_precision2, roofline (with the in-run PMC passes), latency_b1,\n"
+                         "cpu_baseline; the --no-* options drop single legs of a --full run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the waveforms the last timed step returned to DIR/*.npy (float32, at most 64 MB: see dump_outputs)")
     ap.add_argument("--no-secondary-precision", action="store_true", help="skip the value_precision2 leg")
     ap.add_argument("--no-batch-check", action="store_true", help="skip the batch-vs-single leg (a kernel trace of the run then holds the step's launches only)")
     ap.add_argument("--config", choices=["kokoro", "whisper", "qwen3", "csm", "kitten", "dsp"], default="kokoro",
@@ -67,8 +76,40 @@ def parse():
     ap.add_argument("--no-pmc", action="store_true", help="skip the two in-run rocprofv3 PMC passes (roofline.traffic is then null)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--shape-table", default="", help="write the per-shape conv_gemm timing table (roofline leg) to this file")
-    return ap.parse_known_args()[0]
+    ap.add_argument("--shape-table", default="", help="write the per-shape conv_gemm timing table (roofline leg, needs --full) to this file")
+    args = ap.parse_known_args()[0]
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.shape_table and not args.full:
+        ap.error("--shape-table needs --full (it is written by the roofline leg)")
+    if args.dump_outputs and args.config != "kokoro":
+        ap.error("--dump-outputs is implemented for the Kokoro line only")
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_batch_check = args.no_secondary_precision = args.no_roofline = args.no_latency = args.no_cpu_baseline = True
+    return args
+
+
+DUMP_BUDGET_BYTES = 63_000_000   # 64 MB in all, less headroom for the .npy headers
+
+
+def dump_outputs(path, outs):
+    """``--dump-outputs DIR``: what a caller of the timed path receives from its last step, the waveforms of every utterance, in float32.
+    ``waveforms.npy`` is [utterances, samples] when all have one length (the canonical batch: 64 x 158 400 = 40.6 MB), else their concatenation
+    in item order; ``lengths.npy`` holds the samples per utterance.  Above DUMP_BUDGET_BYTES a fixed seeded sample of the concatenation is written
+    instead, its positions in ``waveforms_index.npy``."""
+    os.makedirs(path, exist_ok=True)
+    w = [o.detach().to("cpu", torch.float32).reshape(-1).numpy() for o in outs]
+    lengths = np.array([a.size for a in w], dtype=np.float64)
+    flat = np.concatenate(w)
+    if flat.nbytes + lengths.nbytes > DUMP_BUDGET_BYTES:
+        n = (DUMP_BUDGET_BYTES - lengths.nbytes) // 12   # float32 value + float64 position per sample
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.size, size=n))
+        np.save(os.path.join(path, "waveforms_index.npy"), idx.astype(np.float64))
+        arr = flat[idx]
+    else:
+        arr = flat.reshape(len(w), -1) if len(set(lengths.tolist())) == 1 else flat
+    np.save(os.path.join(path, "waveforms.npy"), arr)
+    np.save(os.path.join(path, "lengths.npy"), lengths)
 
 
 def cpu_baseline_child():
@@ -405,6 +446,8 @@ def main():
     if rank == 0:
         assert len(outs) == n_total and all(o.numel() == f_of[i] * 600 for i, o in enumerate(outs))
         assert bool(torch.isfinite(torch.cat([o.reshape(-1) for o in outs])).all())   # one fused check, after the timed region
+        if args.dump_outputs:   # before any other leg runs the engine again
+            dump_outputs(args.dump_outputs, outs)
 
     # ---- after the timed region (N = 1): the benchmarked step against the SAME utterance run alone, SineGen inputs fixed on both sides
     batch_check = None
