@@ -245,6 +245,57 @@ int mi355_layernorm(const mi355_layernorm_args* a, void* stream);
 int mi355_split16(const float* x, void* y, int64_t n, int32_t fmt, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GroupNorm with ONE group (ABI 37): per SAMPLE mean / biased variance over all (time x channel) elements, then a per-channel
+ * weight and bias.  Replaces nn.GroupNorm(1, C, pytorch_compatible=True) behind every conv of the 48 kHz EnCodec
+ * (codec/models/encodec/encodec.py:172-291, norm_type = "time_group_norm").  Three steps, so that the normalised tensor is
+ * written only where something other than a conv prologue consumes it:
+ *   statistics -> coefficients scale[b, c] = weight[c] * rstd[b], shift[b, c] = bias[c] - mean[b] * scale[b, c]
+ *   (the shape of mi355_conv_gemm_args.pre_scale / pre_shift) -> apply.
+ * ------------------------------------------------------------------------------------------ */
+#define MI355_GN_PART_ELEMS 4096
+/* Statistics pass: one read of x.  The valid elements of a sample (lens[b] rows of C channels) are cut into parts of
+ * MI355_GN_PART_ELEMS consecutive elements, one workgroup each (a 1 s chunk of 48 000 x 32 floats is 375 workgroups); a part
+ * leaves (sum, sum of squared deviations from the part's own mean) as two doubles.  Nothing is accumulated across workgroups:
+ * mi355_group_norm_coef merges the parts in a fixed order. */
+typedef struct {
+  const float* x; int64_t x_bstride; int32_t ldx;   /* [B, L, ldx]; ldx == C reads 16 bytes per lane */
+  int32_t C; int32_t L; const int32_t* lens; int32_t B;   /* lens [B] nullable => L */
+  double* partials; int64_t partials_bstride;   /* [B, >= ceil(L * C / MI355_GN_PART_ELEMS), 2]; bstride in doubles */
+} mi355_group_norm_stats_args;
+int mi355_group_norm_stats(const mi355_group_norm_stats_args* a, void* stream);
+
+/* Coefficients from partial statistics, merged in float64 with Chan's formula (first the total sum -> the mean, then
+ * M2 = sum_e [M2_e + cnt_e (mean_e - mean)^2]).  conv_partials = 0: `partials` is what mi355_group_norm_stats wrote (doubles);
+ * conv_partials = 1: `partials` is the stats_partial buffer of a mi355_conv_gemm epilogue, float [B, ceil(L / MI355_STATS_ROWS), C, 2],
+ * merged over row blocks AND channels.  The coefficients are laid out `rep` times: scale[b, q * C + c] for q < rep (a strided conv
+ * that reads regrouped rows [rows / rep, rep * C]); columns from rep * C to out_ld are zero. */
+typedef struct {
+  const void* partials; int64_t partials_bstride;   /* bstride in elements of the buffer's type */
+  int32_t conv_partials;
+  int32_t C; int32_t L; const int32_t* lens; int32_t B;
+  const float* weight; const float* bias;   /* [C]; nullable => 1 / 0 */
+  float eps;
+  int32_t rep;         /* 0 => 1 */
+  float* scale; float* shift; int32_t out_ld;   /* [B, out_ld], out_ld >= rep * C */
+  float* mean_rstd;    /* nullable; [B, 2] */
+} mi355_group_norm_coef_args;
+int mi355_group_norm_coef(const mi355_group_norm_coef_args* a, void* stream);
+
+/* y[b, l, c] = x0[b, l + row_off0, c] * scale0[b, c] + shift0[b, c]  (+ x1[b, l + row_off1, c] * scale1[b, c] + shift1[b, c]),
+ * one pass, 16-byte accesses when C, the strides and the pointers allow.  scale1 == NULL with x1 set adds x1 as it is.
+ * The two-operand form is the resnet block's shortcut_norm(...) + norm2(...); the row offset is the transposed conv's trim. */
+typedef struct {
+  const float* x0; int64_t x0_bstride; int32_t ldx0; int32_t row_off0;
+  const float* scale0; const float* shift0;
+  const float* x1; int64_t x1_bstride; int32_t ldx1; int32_t row_off1;   /* nullable */
+  const float* scale1; const float* shift1;                              /* nullable (together) */
+  int32_t coef_ld;     /* row stride of all coefficient arrays */
+  int32_t C; int32_t L; int32_t B;   /* L = output rows */
+  float* y; int64_t y_bstride; int32_t ldy;
+} mi355_group_norm_apply_args;
+int mi355_group_norm_apply(const mi355_group_norm_apply_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bidirectional LSTM recurrence (the x-projection is a conv_gemm).
  * Replaces the per-time-step Python loops of LSTM._forward_direction/_backward_direction
  * (modules.py:150-240): gates i,f,g,o; c = f*c + i*g; h = o*tanh(c).

@@ -18,7 +18,12 @@ Encode side (round 5; encodec.py:340-389, 445-533, 556-650), from the same kerne
 it; the strided ``EncodecConv1d(K = 2 r, stride r)`` is a TWO-tap conv over the padded rows regrouped ``[rows / r, r * C]`` (the padding makes the
 row count a whole number of strides by construction, encodec.py:202-210); the LSTM as in the decoder; ``quantizer.encode`` is ONE
 ``mi355_rvq_encode`` launch (residual kept on chip across the layers in use for the bandwidth).
-``norm_type = "time_group_norm"`` (the 48 kHz model's GroupNorm after every conv) is not built.  Weights: float32 checkpoints are held as fp16 MFMA images, activations split fp16 hi + lo
+``norm_type = "time_group_norm"`` (the 48 kHz model, encodec.py:172-291: ``GroupNorm(1, C)`` behind every conv and transposed conv): a conv's raw output
+gets one statistics pass (``mi355_group_norm_stats``) and per-(sample, channel) coefficients (``mi355_group_norm_coef``); the normalisation itself is
+the affine PROLOGUE of the conv that consumes the tensor (reflect padding gathers raw rows, which commutes with a per-channel affine and the ELU) and
+is written out (``mi355_group_norm_apply``) only where it is summed -- the resnet block's ``shortcut_norm(...) + norm2(...)``, the LSTM skip -- at the
+final outputs and in front of zero padding.  The transposed conv stores its FULL output (the reference normalises before its trim), the trim is a
+row offset of the consumer.  All chunks of one ``encode`` / ``decode`` call run as one batch of B * n_chunks samples.  Weights: float32 checkpoints are held as fp16 MFMA images, activations split fp16 hi + lo
 (``precision = 4``); deviation from the float32 oracle asserted in ``tests/test_encodec_gpu.py``.
 """
 from __future__ import annotations
@@ -137,15 +142,29 @@ def num_quantizers(c: dict) -> int:
     return int(1000 * c["target_bandwidths"][-1] // (frame_rate * 10))
 
 
+def _add_norm_weights(w: Dict[str, torch.Tensor], c: dict, convs, seed: int) -> None:
+    """``<layer>.norm.weight`` / ``.norm.bias`` of a ``time_group_norm`` model, from a generator of their own (the conv / LSTM / codebook tensors of a
+    seed are the same with and without them); away from the identity, so that a dropped affine shows."""
+    if c["norm_type"] != "time_group_norm":
+        return
+    g = torch.Generator().manual_seed(seed)
+    for name, cout in convs:
+        w[name + ".norm.weight"] = 1.0 + 0.2 * torch.randn(cout, generator=g)
+        w[name + ".norm.bias"] = 0.1 * torch.randn(cout, generator=g)
+
+
 def make_encodec_weights(config, seed: int = 0) -> Dict[str, torch.Tensor]:
     """Random float32 decode-side parameters of the shapes ``Encodec(config)`` allocates (reference module paths, MLX layouts)."""
     c = _cfg_dict(config)
     g = torch.Generator().manual_seed(seed)
     w: Dict[str, torch.Tensor] = {}
 
+    convs = []
+
     def conv(name, cout, k, cin, gain=1.0):
         w[name + ".conv.weight"] = (torch.rand(cout, k, cin, generator=g) * 2 - 1) * math.sqrt(3.0 / (cin * k)) * gain
         w[name + ".conv.bias"] = 0.02 * torch.randn(cout, generator=g)
+        convs.append((name, cout))
 
     names = decoder_layer_names(c)
     scaling = int(2 ** len(c["upsampling_ratios"]))
@@ -169,6 +188,7 @@ def make_encodec_weights(config, seed: int = 0) -> Dict[str, torch.Tensor]:
     conv(names["conv_out"], c["audio_channels"], c["last_kernel_size"], c["num_filters"], gain=0.5)
     for i in range(num_quantizers(c)):
         w[f"quantizer.layers.{i}.codebook.embed"] = torch.randn(c["codebook_size"], c["codebook_dim"], generator=g) / math.sqrt(i + 1.0)
+    _add_norm_weights(w, c, convs, seed + 32452843)
     return w
 
 
@@ -178,9 +198,12 @@ def make_encodec_encoder_weights(config, seed: int = 0) -> Dict[str, torch.Tenso
     g = torch.Generator().manual_seed(seed + 15485863)
     w: Dict[str, torch.Tensor] = {}
 
+    convs = []
+
     def conv(name, cout, k, cin, gain=1.0):
         w[name + ".conv.weight"] = (torch.rand(cout, k, cin, generator=g) * 2 - 1) * math.sqrt(3.0 / (cin * k)) * gain
         w[name + ".conv.bias"] = 0.02 * torch.randn(cout, generator=g)
+        convs.append((name, cout))
 
     names = encoder_layer_names(c)
     conv(names["conv_in"], c["num_filters"], c["kernel_size"], c["audio_channels"], gain=2.0)
@@ -202,6 +225,7 @@ def make_encodec_encoder_weights(config, seed: int = 0) -> Dict[str, torch.Tenso
         w[p + "Wh"] = (torch.rand(4 * dim, dim, generator=g) * 2 - 1) / math.sqrt(dim)
         w[p + "bias"] = 0.1 * torch.randn(4 * dim, generator=g)
     conv(names["conv_out"], c["hidden_size"], c["last_kernel_size"], dim, gain=1.5)
+    _add_norm_weights(w, c, convs, seed + 49979687)
     return w
 
 
@@ -267,14 +291,27 @@ class _Quantizer:
         return z
 
 
+class _GN:
+    """A conv output whose GroupNorm is still pending: the normalised tensor is ``raw[:, off:off + rows] * scale + shift`` with the per-(sample,
+    channel) coefficients ``coef`` = (scale, shift) taken over ALL rows of ``raw`` (the transposed conv is normalised before its trim)."""
+    __slots__ = ("raw", "coef", "off", "rows")
+
+    def __init__(self, raw, coef, off=0, rows=None):
+        self.raw, self.coef, self.off, self.rows = raw, coef, off, raw.shape[1] - off if rows is None else rows
+
+    def view(self) -> torch.Tensor:
+        return self.raw[:, self.off:self.off + self.rows]
+
+
 class Encodec:
     def __init__(self, config, weights: Optional[Dict[str, torch.Tensor]] = None, device="cuda:0", seed: int = 0):
         """``config``: ``EncodecConfig`` or a dict of its fields; ``weights``: reference parameter names (omitted: random, like a freshly constructed model)."""
         ops.require_gpu()
         self.config = config if isinstance(config, EncodecConfig) else EncodecConfig(**{k: v for k, v in dict(config).items() if k in EncodecConfig.__dataclass_fields__})
         self.c = _cfg_dict(config)
-        if self.c["norm_type"] != "weight_norm":
-            raise NotImplementedError("norm_type 'time_group_norm' (GroupNorm after every conv, the 48 kHz model) is not built")
+        if self.c["norm_type"] not in ("weight_norm", "time_group_norm"):
+            raise ValueError(f"norm_type {self.c['norm_type']!r}")
+        self.gn = self.c["norm_type"] == "time_group_norm"
         if self.c["pad_mode"] not in ("reflect", "constant", "zero"):
             raise ValueError(f"pad_mode {self.c['pad_mode']!r}")
         self.device = torch.device(device)
@@ -288,8 +325,18 @@ class Encodec:
         w = {k: torch.as_tensor(v).detach().float().cpu() for k, v in weights.items() if k.startswith(("decoder.", "quantizer.", "encoder."))}
         names = decoder_layer_names(c)
 
+        def norm_of(pc: PackedConv, name: str) -> PackedConv:
+            """``time_group_norm``: the layer's GroupNorm affine rides on its packed conv (``pc.gn`` = (weight, bias) on the device)."""
+            if self.gn:
+                miss = [k for k in (name + ".norm.weight", name + ".norm.bias") if k not in w]
+                if miss and strict:
+                    raise KeyError(f"Encodec.load_weights: missing {miss} (norm_type = 'time_group_norm')")
+                n = w[name + ".conv.weight"].shape[0]
+                pc.gn = (w.get(name + ".norm.weight", torch.ones(n)).contiguous().to(dev), w.get(name + ".norm.bias", torch.zeros(n)).contiguous().to(dev))
+            return pc
+
         def conv(name) -> PackedConv:
-            return ops.pack_conv(w[name + ".conv.weight"], w.get(name + ".conv.bias"), dev, f16=True)
+            return norm_of(ops.pack_conv(w[name + ".conv.weight"], w.get(name + ".conv.bias"), dev, f16=True), name)
 
         self.quantizer = _Quantizer(w, c, dev)
         self.conv_in = conv(names["conv_in"])
@@ -305,13 +352,15 @@ class Encodec:
             res = []
             for r in blk["res"]:
                 res.append(dict(c1=conv(r + ".block.1"), c2=conv(r + ".block.3"), sc=conv(r + ".shortcut") if c["use_conv_shortcut"] else None))
-            self.blocks.append(dict(ratio=ratio, cout=up_w.shape[0], up=ops.pack_conv_transpose(up_w, w.get(blk["up"] + ".conv.bias"), ratio, dev, f16=True), res=res))
+            for j, rb in enumerate(res):
+                rb["dil"] = c["dilation_growth_rate"] ** j   # (read by the time_group_norm schedule)
+            self.blocks.append(dict(ratio=ratio, cout=up_w.shape[0], up=norm_of(ops.pack_conv_transpose(up_w, w.get(blk["up"] + ".conv.bias"), ratio, dev, f16=True), blk["up"]), res=res))
         self.conv_out = conv(names["conv_out"])
         self.enc = None
         if "encoder.layers.0.conv.weight" in w:   # the encode half (encodec.py:340-389)
             en = encoder_layer_names(c)
             w0 = w[en["conv_in"] + ".conv.weight"]   # [F, K, channels] -> one tap of K * channels "channels" (flattened conv over the padded samples)
-            stem = ops.pack_conv(w0.reshape(w0.shape[0], 1, w0.shape[1] * w0.shape[2]).contiguous(), w.get(en["conv_in"] + ".conv.bias"), dev, f16=True)
+            stem = norm_of(ops.pack_conv(w0.reshape(w0.shape[0], 1, w0.shape[1] * w0.shape[2]).contiguous(), w.get(en["conv_in"] + ".conv.bias"), dev, f16=True), en["conv_in"])
             eblocks = []
             for blk, ratio in zip(en["blocks"], reversed(c["upsampling_ratios"])):
                 res = []
@@ -322,7 +371,7 @@ class Encodec:
                 cout, k, cin = wd.shape
                 if k != 2 * ratio:
                     raise ValueError(f"{blk['down']}: {k} taps for stride {ratio} (the reference builds kernel_size = 2 * ratio)")
-                eblocks.append(dict(ratio=ratio, cin=cin, res=res, down=ops.pack_conv(wd.reshape(cout, 2, ratio * cin).contiguous(), w.get(blk["down"] + ".conv.bias"), dev, f16=True)))
+                eblocks.append(dict(ratio=ratio, cin=cin, res=res, down=norm_of(ops.pack_conv(wd.reshape(cout, 2, ratio * cin).contiguous(), w.get(blk["down"] + ".conv.bias"), dev, f16=True), blk["down"])))
             elstm = []
             for l in range(c["num_lstm_layers"]):
                 p = f"{en['lstm']}.lstm.{l}."
@@ -379,6 +428,8 @@ class Encodec:
         B, L, ch = x.shape
         if ch != c["audio_channels"]:
             raise ValueError(f"encoder: {ch} audio channels given, the model has {c['audio_channels']}")
+        if self.gn:
+            return self._encoder_gn(x, return_stages)
         st = {}
         xp = self._padded(x, e["k0"], 1)                                  # [B, L + K - 1, ch]: the taps of a row are contiguous samples
         h = self._f(B, L, e["stem"].cout)
@@ -456,6 +507,13 @@ class Encodec:
         step = chunk_length - stride
         if (input_length % stride) != step:
             raise ValueError("The input length is not properly padded for batched chunked encoding. Make sure to pad the input correctly.")
+        if self.gn:   # chunks are independent (non-causal convs, per-chunk statistics and scale, zero LSTM state): ONE batch of n_chunks * B samples
+            offs = list(range(0, input_length - step, stride))
+            n, B = len(offs), input_values.shape[0]
+            x = torch.stack([input_values[:, o:o + chunk_length] for o in offs]).reshape(n * B, chunk_length, channels)
+            m = torch.stack([padding_mask[:, o:o + chunk_length].bool() for o in offs]).reshape(n * B, chunk_length)
+            codes, scale = self._encode_frame(x, bandwidth, m)
+            return codes.view(n, B, *codes.shape[1:]), [None] * n if scale is None else list(scale.view(n, B, 1, 1))
         frames, scales = [], []
         for offset in range(0, input_length - step, stride):
             mask = padding_mask[:, offset:offset + chunk_length].bool()
@@ -497,6 +555,8 @@ class Encodec:
     def _decoder(self, z: torch.Tensor, return_stages: bool = False):
         """z [B, T, hidden_size] -> [B, T * prod(ratios), audio_channels] (encodec.py:391-444)."""
         c = self.c
+        if self.gn:
+            return self._decoder_gn(z, return_stages)
         B, T, _ = z.shape
         st = {}
         dim = self.conv_in.cout
@@ -538,6 +598,112 @@ class Encodec:
         self._conv(h, self.conv_out, out, elu=True)
         return (out, st) if return_stages else out
 
+    # ------------------------------------------------------------------ time_group_norm schedule (encodec.py:172-291, 305-337)
+    def _gn_of(self, raw: torch.Tensor, pc: PackedConv, off: int = 0, rows: Optional[int] = None) -> _GN:
+        """Statistics over ALL of ``raw`` [B, L, C] (one read) -> the layer's coefficients; nothing is normalised yet."""
+        coef = ops.group_norm_coef(ops.group_norm_stats(raw), raw.shape[1], raw.shape[2], pc.gn[0], pc.gn[1], eps=1e-5)
+        return _GN(raw, coef, off, rows)
+
+    def _gn_mat(self, x) -> torch.Tensor:
+        """The normalised tensor itself (for a sum, an output, or zero padding -- a padded 0 would become ``shift`` in a prologue)."""
+        if not isinstance(x, _GN):
+            return x
+        y = self._f(x.raw.shape[0], x.rows, x.raw.shape[2])
+        return ops.group_norm_apply(x.raw, x.coef, y, row_off0=x.off)
+
+    def _gn_conv(self, x, pc: PackedConv, *, dilation: int = 1, elu: bool = False) -> _GN:
+        """``norm(conv(ELU?(x)))`` with the norm left pending; a pending norm of ``x`` becomes this conv's affine prologue."""
+        pre = None
+        if isinstance(x, _GN):
+            if pc.k > 1 and self.c["pad_mode"] != "reflect":
+                x = self._gn_mat(x)
+            else:
+                pre, x = x.coef, x.view()
+        xp = self._padded(x, pc.k, dilation)
+        L = xp.shape[1] - (pc.k - 1) * dilation
+        y = self._f(xp.shape[0], L, pc.cout)
+        ops.conv_gemm(xp, pc, y, dil=dilation, pad=0, lout=L, pre=pre, pre_act=ACT_ELU if elu else ACT_NONE, precision=4)
+        return self._gn_of(y, pc)
+
+    def _gn_resnet(self, x, rb: dict) -> torch.Tensor:
+        """``shortcut_norm(shortcut(x)) + norm2(conv2(ELU(norm1(conv1(ELU(x))))))``: the sum is the one place the block writes a normalised tensor."""
+        hid = self._gn_conv(x, rb["c1"], dilation=rb["dil"], elu=True)
+        o = self._gn_conv(hid, rb["c2"], elu=True)
+        out = torch.empty_like(o.raw)
+        if rb["sc"] is not None:
+            s = self._gn_conv(x, rb["sc"])
+            return ops.group_norm_apply(s.raw, s.coef, out, o.raw, o.coef)
+        return ops.group_norm_apply(o.raw, o.coef, out, self._gn_mat(x))
+
+    def _gn_lstm(self, h0: _GN, layers) -> torch.Tensor:
+        """``EncodecLSTM``: lstm(norm(h0)) + norm(h0) -- the first x-projection takes the norm as its prologue, the skip is the two-operand apply."""
+        B, T, _ = h0.raw.shape
+        y, pre = h0.view(), h0.coef
+        for l in layers:
+            xq = self._f(B, T, 4 * l["H"])
+            ops.conv_gemm(y, l["wx"], xq, pre=pre, precision=4)
+            out = self._f(B, T, l["H"])
+            ops.lstm_seq(xq, l["wh"], out)
+            y, pre = out, None
+        if pre is not None:   # no LSTM layers: x + x
+            y = self._gn_mat(h0)
+        return ops.group_norm_apply(h0.raw, h0.coef, torch.empty_like(h0.raw), y)
+
+    def _encoder_gn(self, x: torch.Tensor, return_stages: bool = False):
+        c, e = self.c, self.enc
+        B, L, ch = x.shape
+        st = {}
+        xp = self._padded(x, e["k0"], 1)
+        raw = self._f(B, L, e["stem"].cout)
+        ops.conv_gemm(xp, e["stem"], raw, lout=L, flat=dict(ldx=ch, x_off=0, channels=ch), precision=4)
+        h = self._gn_of(raw, e["stem"])
+        if return_stages:
+            st["conv_in"] = self._gn_mat(h)
+        for bi, blk in enumerate(e["blocks"]):
+            r, C = blk["ratio"], blk["cin"]
+            for rb in blk["res"]:
+                h = self._gn_resnet(h, rb)
+            hp = self._padded(self._gn_mat(h), 2 * r, 1, stride=r)          # materialised: the block's sum (or, without residual layers, one apply)
+            assert hp.shape[1] % r == 0, (hp.shape, r)
+            rows = hp.shape[1] // r
+            L = rows - 1
+            y = self._f(B, L, blk["down"].cout)
+            ops.conv_gemm(hp.view(B, rows, r * C), blk["down"], y, pad=0, lout=L, pre_act=ACT_ELU, precision=4)
+            h = self._gn_of(y, blk["down"])
+            if return_stages:
+                st[f"block{bi}"] = self._gn_mat(h)
+        h = self._gn_lstm(h, e["lstm"])
+        st["lstm"] = h
+        z = self._gn_mat(self._gn_conv(h, e["out"], elu=True))
+        st["embeddings"] = z
+        return (z, st) if return_stages else z
+
+    def _decoder_gn(self, z: torch.Tensor, return_stages: bool = False):
+        c = self.c
+        st = {}
+        h0 = self._gn_conv(z.contiguous(), self.conv_in)
+        if return_stages:
+            st["conv_in"] = self._gn_mat(h0)
+        h = self._gn_lstm(h0, self.lstm)
+        st["lstm"] = h
+        B = h.shape[0]
+        for bi, blk in enumerate(self.blocks):
+            s, cout, taps = blk["ratio"], blk["cout"], blk["up"].k
+            Lin = h.shape[1]
+            padding_total = s
+            pr = math.ceil(padding_total * c["trim_right_ratio"]) if c["use_causal_conv"] else padding_total // 2
+            pl = padding_total - pr
+            full = (Lin + 1) * s                                   # the reference normalises the FULL transposed conv, then trims (encodec.py:275-291)
+            raw = self._f(B, full, cout)
+            ops.conv_gemm(h, blk["up"], raw, pad=taps - 1, lout=Lin + taps - 1, up=dict(s=s, p=0, cout=cout, lout=full), pre_act=ACT_ELU, precision=4)
+            y = self._gn_of(raw, blk["up"], off=pl, rows=full - padding_total)
+            for rb in blk["res"]:
+                y = self._gn_resnet(y, rb)
+            h = self._gn_mat(y)
+            st[f"block{bi}"] = h
+        out = self._gn_mat(self._gn_conv(h, self.conv_out, elu=True))
+        return (out, st) if return_stages else out
+
     def _decode_frame(self, codes, scale=None) -> torch.Tensor:
         out = self._decoder(self.quantizer.decode(codes))
         return out * torch.as_tensor(scale).to(out.device) if scale is not None else out
@@ -569,6 +735,11 @@ class Encodec:
             if audio_codes.shape[1] != 1:
                 raise ValueError(f"Expected one frame, got {len(audio_codes)}")
             audio = self._decode_frame(audio_codes[:, 0], audio_scales[0])
+        elif self.gn:   # all chunks as one batch (see encode)
+            n, B = audio_codes.shape[:2]
+            sc = None if audio_scales[0] is None else torch.cat([torch.as_tensor(s).to(self.device).reshape(B, 1, 1) for s in audio_scales])
+            out = self._decode_frame(audio_codes.reshape(n * B, *audio_codes.shape[2:]), sc)
+            audio = self._linear_overlap_add(list(out.view(n, B, *out.shape[1:])), self.chunk_stride or 1)
         else:
             audio = self._linear_overlap_add([self._decode_frame(f, s) for f, s in zip(audio_codes, audio_scales)], self.chunk_stride or 1)
         if padding_mask is not None and padding_mask.shape[1] < audio.shape[1]:

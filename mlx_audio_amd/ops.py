@@ -593,6 +593,63 @@ def adain_from_partials(stats: torch.Tensor, L: int, gb: Optional[torch.Tensor],
     return scale, shift
 
 
+GN_PART_ELEMS = 4096  # MI355_GN_PART_ELEMS
+
+
+def group_norm_stats(x: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-sample partial statistics of ``x`` [B, L, C] for a one-group GroupNorm (``mi355_group_norm_stats``): float64
+    [B, ceil(L * C / GN_PART_ELEMS), 2] = (sum, sum of squared deviations from the part's mean) per part of consecutive elements."""
+    B, L, C, xbs, ldx = _nlc(x)
+    assert x.dtype == torch.float32
+    parts = torch.empty((B, (L * C + GN_PART_ELEMS - 1) // GN_PART_ELEMS, 2), dtype=torch.float64, device=x.device)
+    _lib.call_struct("mi355_group_norm_stats", "mi355_group_norm_stats_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, C=C, L=L, lens=_ptr(lens), B=B,
+                     partials=_ptr(parts), partials_bstride=parts.stride(0))
+    return parts
+
+
+def group_norm_coef(partials: torch.Tensor, L: int, C: int, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], *, eps: float = 1e-5,
+                    lens: Optional[torch.Tensor] = None, rep: int = 1, return_stats: bool = False):
+    """GroupNorm(1, C) coefficients (scale, shift), each [B, rep * C padded to 32] -- the ``pre=`` operands of ``conv_gemm`` -- from the partials of
+    ``group_norm_stats`` (float64 [B, parts, 2]) or from the ``stats=`` buffer a conv epilogue wrote (float32 [B, blocks, C, 2], merged over blocks and
+    channels).  ``rep``: the coefficient row repeated for a strided conv that reads regrouped rows [rows / rep, rep * C].
+    ``return_stats`` adds the per-sample (mean, rstd) [B, 2]."""
+    conv = partials.dim() == 4
+    assert partials.is_contiguous() and partials.dtype == (torch.float32 if conv else torch.float64)
+    assert (partials.shape[2] == C and partials.shape[3] == 2) if conv else partials.shape[2] == 2
+    B = partials.shape[0]
+    ld = round_up(rep * C, 32)
+    scale = torch.empty((B, ld), dtype=torch.float32, device=partials.device)
+    shift = torch.empty((B, ld), dtype=torch.float32, device=partials.device)
+    mr = torch.empty((B, 2), dtype=torch.float32, device=partials.device) if return_stats else None
+    _lib.call_struct("mi355_group_norm_coef", "mi355_group_norm_coef_args", _stream(), partials=_ptr(partials), partials_bstride=partials.stride(0),
+                     conv_partials=int(conv), C=C, L=L, lens=_ptr(lens), B=B, weight=_ptr(weight), bias=_ptr(bias), eps=eps, rep=rep,
+                     scale=_ptr(scale), shift=_ptr(shift), out_ld=ld, mean_rstd=_ptr(mr))
+    return (scale, shift, mr) if return_stats else (scale, shift)
+
+
+def group_norm_apply(x0: torch.Tensor, coef0, y: torch.Tensor, x1: Optional[torch.Tensor] = None, coef1=None, *, row_off0: int = 0, row_off1: int = 0):
+    """``y = x0[:, row_off0:] * scale0 + shift0 (+ x1[:, row_off1:] * scale1 + shift1, or + x1 when coef1 is None)`` over the rows of ``y`` [B, L, C]
+    (``mi355_group_norm_apply``); ``coef*`` = (scale, shift) of ``group_norm_coef``."""
+    B, L, C, ybs, ldy = _nlc(y)
+    B0, L0, C0, x0bs, ldx0 = _nlc(x0)
+    sc0, sh0 = coef0
+    assert B0 == B and C0 == C and row_off0 >= 0 and L0 >= L + row_off0 and sc0.stride(0) == sh0.stride(0) and sc0.shape[0] == B and sc0.stride(1) == 1
+    kw = dict(x0=_ptr(x0), x0_bstride=x0bs, ldx0=ldx0, row_off0=row_off0, scale0=_ptr(sc0), shift0=_ptr(sh0), coef_ld=sc0.stride(0), C=C, L=L, B=B,
+              y=_ptr(y), y_bstride=ybs, ldy=ldy)
+    if x1 is not None:
+        B1, L1, C1, x1bs, ldx1 = _nlc(x1)
+        assert B1 == B and C1 == C and row_off1 >= 0 and L1 >= L + row_off1
+        kw.update(x1=_ptr(x1), x1_bstride=x1bs, ldx1=ldx1, row_off1=row_off1)
+        if coef1 is not None:
+            sc1, sh1 = coef1
+            assert sc1.stride(0) == sc0.stride(0) and sh1.stride(0) == sc0.stride(0) and sc1.shape[0] == B
+            kw.update(scale1=_ptr(sc1), shift1=_ptr(sh1))
+    else:
+        assert coef1 is None
+    _lib.call_struct("mi355_group_norm_apply", "mi355_group_norm_apply_args", _stream(), **kw)
+    return y
+
+
 def layernorm(x: torch.Tensor, y: torch.Tensor, *, weight=None, bias=None, ada_gb=None, res=None, eps=1e-5,
               lens=None, post_act=ACT_NONE, post_slope=0.0, split: int = 0):
     """``split`` = 2 / 4: ``y`` receives SPLIT words (``conv_gemm(..., x_split=True)`` at that precision reads them) instead of floats."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Measurement line for the widened codec rows: Vocos (mel -> waveform, 24 kHz), DAC (44 kHz, 9 codebooks), EnCodec (24 kHz, 6 kbps), SNAC
-(24 kHz, 3 code levels) decode and the BigVGAN vocoder (22 kHz, 80 bands) on one MI355X, synthetic weights of the published shapes, inputs resident in HBM before the timed region.
+(24 kHz, 3 code levels) decode, EnCodec 48 kHz stereo (``--only encodec48``: ``time_group_norm``, one clip of ``--seconds`` as 1 s chunks, batched and chunk by chunk) and the BigVGAN vocoder (22 kHz, 80 bands) on one MI355X, synthetic weights of the published shapes, inputs resident in HBM before the timed region.
 
 Prints ONE JSON line per codec: value = audio samples decoded per second over the whole batch (and x real time), ms per batch, and a roofline
 object for the conv_gemm launches of one instrumented pass (algorithmic FLOPs / summed launch durations against the dense bf16-class MFMA
@@ -114,6 +114,35 @@ def encode_lines(args, dev, g, dt16):
                                   conv_roofline(fn), dt16, T, 8 * T)))
 
 
+ENCODEC_48K = dict(audio_channels=2, num_filters=32, upsampling_ratios=[8, 5, 4, 2], hidden_size=128, num_lstm_layers=2, codebook_size=1024, codebook_dim=128,
+                   target_bandwidths=[3.0, 6.0, 12.0, 24.0], sampling_rate=48000, chunk_length_s=1.0, overlap=0.01, use_causal_conv=False, normalize=True,
+                   norm_type="time_group_norm", pad_mode="reflect")
+
+
+def encodec48_chunks(seconds):
+    """1 s chunks at 1 % overlap covering ``seconds`` of audio (30 s -> 31 chunks)."""
+    chunk, stride = 48000, 47520
+    return chunk, stride, max(1, -(-(int(seconds * 48000) - chunk) // stride) + 1)
+
+def encodec48_encode_lines(args, dev, g, dt16):
+    """EnCodec 48 kHz (``time_group_norm``) encode of ONE stereo clip: all chunks as one batch (the product path) and chunk by chunk (the reference's loop)."""
+    from mlx_audio_amd.codec.models.encodec import Encodec
+
+    eng = Encodec(ENCODEC_48K, device=dev, seed=0)
+    chunk, stride, n = encodec48_chunks(args.seconds)
+    total = (n - 1) * stride + chunk
+    x = (0.3 * torch.randn(1, total, 2, generator=g)).to(dev)
+    m = torch.ones(1, total, dtype=torch.bool, device=dev)
+    batched = lambda: eng.encode(x, m, bandwidth=6.0)[0]  # noqa: E731
+    looped = lambda: torch.stack([eng._encode_frame(x[:, o:o + chunk], 6.0, m[:, o:o + chunk])[0] for o in range(0, total - (chunk - stride), stride)])  # noqa: E731
+    for name, fn in (("all chunks as one batch", batched), ("chunk by chunk", looped)):
+        out, wall, dms = timed(fn, args.steps, args.warmup)
+        T = int(out.shape[-1])
+        print(json.dumps(enc_line(f"EnCodec 48 kHz stereo (time_group_norm, 32 filters, rates 2/4/5/8, two 512-wide LSTM layers, 6 kbps = 4 of 16 codebooks), {name}",
+                                  f"1 x {total} stereo samples = {n} chunks of 1 s -> codes (SEANet encoder with GroupNorm behind every conv; LSTM = {2 * T} step launches per "
+                                  f"{'call' if fn is batched else 'chunk'})", 48000, total, 1, wall, dms, conv_roofline(fn), dt16, n * T, n * 4 * T)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -129,7 +158,24 @@ def main():
     dt16 = "fp32 checkpoints held as fp16 MFMA images x fp32 activations (fp16 hi+lo split, fp32 accumulate)"
 
     if args.encode:
+        if args.only in ("", "encodec48"):
+            encodec48_encode_lines(args, dev, g, dt16)
         return encode_lines(args, dev, g, dt16)
+
+    if args.only in ("", "encodec48"):
+        from mlx_audio_amd.codec.models.encodec import Encodec
+
+        eng = Encodec(ENCODEC_48K, device=dev, seed=0)
+        chunk, stride, n = encodec48_chunks(args.seconds)
+        codes = torch.randint(0, 1024, (n, 1, 4, 150), generator=g).to(dev)   # 6 kbps: 4 codebooks, 150 frames per 1 s chunk
+        scales = [torch.full((1, 1, 1), 0.1 + 0.01 * i, device=dev) for i in range(n)]
+        batched = lambda: eng.decode(codes, scales)  # noqa: E731
+        looped = lambda: eng._linear_overlap_add([eng._decode_frame(f, s_) for f, s_ in zip(codes, scales)], stride)  # noqa: E731
+        for name, fn in (("all chunks as one batch", batched), ("chunk by chunk", looped)):
+            out, wall, dms = timed(fn, args.steps, args.warmup)
+            print(json.dumps(line(f"EnCodec 48 kHz stereo (time_group_norm, 32 filters, rates 8/5/4/2, two 512-wide LSTM layers, 4 of 16 codebooks = 6 kbps), {name}",
+                                  f"1 x {n} chunks of 150 code frames -> waveform (RVQ decode + SEANet decoder with GroupNorm behind every conv + overlap-add; LSTM = 300 step "
+                                  f"launches per {'call' if fn is batched else 'chunk'})", 48000, int(out.shape[1]), 1, wall, dms, conv_roofline(fn), dt16)))
 
     if args.only in ("", "vocos"):
         from mlx_audio_amd.codec.models.vocos import Vocos
