@@ -296,6 +296,38 @@ typedef struct {
 int mi355_group_norm_apply(const mi355_group_norm_apply_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * S3 speech tokenizer v2 (codec/models/s3/model_v2.py): the FSMN memory block and the FSQ head.  Two entry points added to
+ * ABI 37 (new structs and functions only; no existing layout changed).  Plain float32, a fixed summation order that does not
+ * depend on the launch geometry: two calls on the same bytes give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+#define MI355_FSMN_MAX_TAPS 31
+/* FSMNMultiHeadAttention.forward_fsmn (model_v2.py:152-172), channels-last.  For every b, t < L, c:
+ *   y[b,t,c] = add[b,t,c] + m(b,t) * ( sum_{j<K} w[c,j] * m(b,t+j-left) * v[b,t+j-left,c] + v[b,t,c] ),
+ * m(b,t) = (0 <= t < lens[b]), left = (K - 1) / 2, rows outside [0, L) read as zero.  v is usually the value third of a fused
+ * q|k|v buffer (ldv = 3 C); add is the block's residual stream (NULL: the bare memory term).  K odd, <= MI355_FSMN_MAX_TAPS.
+ * y must not alias v (y may be add). */
+typedef struct {
+  const float* v; int64_t v_bstride; int32_t ldv;       /* [B, L, ldv] */
+  const float* add; int64_t add_bstride; int32_t add_ld; /* nullable; [B, L, add_ld] */
+  const float* w;                                        /* [C, K] */
+  int32_t K; int32_t C; int32_t L; const int32_t* lens; int32_t B;   /* lens [B] nullable => L */
+  float* y; int64_t y_bstride; int32_t ldy;              /* [B, L, ldy] */
+} mi355_fsmn_memory_args;
+int mi355_fsmn_memory(const mi355_fsmn_memory_args* a, void* stream);
+
+/* FSQCodebook.encode (model_v2.py:82-96): h = x w^T + b (8 outputs), codes[row] = sum_d (rint(tanhf(h_d) * 0.9990000128746033f) + 1) * 3^d
+ * (round half to even, full-precision tanhf), one read of x.  With lens, rows = B * L and the rows at or beyond lens[b] give code 0
+ * (and h = 0).  C a multiple of 4, <= 1280; x rows and w 16-byte aligned. */
+typedef struct {
+  const float* x; int32_t ldx; int64_t rows; int32_t C;  /* [rows, ldx] */
+  const float* w; const float* b;                        /* [8, C]; [8] nullable => 0 */
+  const int32_t* lens; int32_t L;                        /* nullable; lens [rows / L] */
+  int32_t* codes;                                        /* [rows] */
+  float* h;                                              /* nullable; [rows, 8] pre-activations */
+} mi355_fsq_encode_args;
+int mi355_fsq_encode(const mi355_fsq_encode_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bidirectional LSTM recurrence (the x-projection is a conv_gemm).
  * Replaces the per-time-step Python loops of LSTM._forward_direction/_backward_direction
  * (modules.py:150-240): gates i,f,g,o; c = f*c + i*g; h = o*tanh(c).

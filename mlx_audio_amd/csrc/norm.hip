@@ -154,9 +154,10 @@ __global__ __launch_bounds__(256) void adain_from_partials_kernel(const mi355_ad
   a.shift[(int64_t)b * a.out_ld + c] = sh;
 }
 
-// one wave per row, up to 1024 channels held in registers (two-pass mean / variance like mx.var)
+// one wave per row, up to 256 * NCH channels held in registers (two-pass mean / variance like mx.var); NCH = 4 for rows of up to 1024 channels,
+// 8 for the wider ones (the S3 tokenizer's 1280)
 // VEC: weight / bias / ada_gb rows are 16-byte aligned (the host checks): float4 operand loads; otherwise four scalar loads each
-template <bool VEC>
+template <bool VEC, int NCH>
 __global__ __launch_bounds__(256) void layernorm_kernel(const mi355_layernorm_args a) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -166,13 +167,13 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const mi355_layernorm_ar
   if (l >= len) return;
   const float* xr = a.x + (int64_t)b * a.x_bstride + (int64_t)l * a.ldx;
   const float* rr = a.res ? a.res + (int64_t)b * a.res_bstride + (int64_t)l * a.ldr : nullptr;
-  float v[4][4];
+  float v[NCH][4];
   float s = 0.f;
   // the per-channel operands are requested WITH the row (16-byte loads), not after the two reductions: behind them they were a second, dependent round trip in
   // every wave's life -- 202 -> ~110 us for Whisper's 96 000 x 768 rows, the time of a plain copy (tools/ln_bench.py)
-  float4 w4[4], b4[4], g4[4], e4[4];
+  float4 w4[NCH], b4[NCH], g4[NCH], e4[NCH];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NCH; ++i) {
     const int c = i * 256 + lane * 4;
     w4[i] = make_float4(1.f, 1.f, 1.f, 1.f); b4[i] = make_float4(0.f, 0.f, 0.f, 0.f); g4[i] = b4[i]; e4[i] = b4[i];
     if (c < a.C) {
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const mi355_layernorm_ar
     }
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NCH; ++i) {
     const int c = i * 256 + lane * 4;
     if (c < a.C) {
       float4 t = *(const float4*)(xr + c);
@@ -201,7 +202,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const mi355_layernorm_ar
   const float mean = wave_sum_fast(s) / (float)a.C;
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NCH; ++i) {
     const int c = i * 256 + lane * 4;
     if (c < a.C) {
 #pragma unroll
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const mi355_layernorm_ar
   const float rstd = 1.0f / sqrtf(var + a.eps);
   float* yr = a.y + (int64_t)b * a.y_bstride + (int64_t)l * a.ldy;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NCH; ++i) {
     const int c = i * 256 + lane * 4;
     if (c < a.C) {
       float o[4];
@@ -296,15 +297,21 @@ extern "C" int mi355_adain_from_partials(const mi355_adain_partials_args* ap, vo
 extern "C" int mi355_layernorm(const mi355_layernorm_args* ap, void* stream) {
   MI355_REQUIRE(ap && ap->x && ap->y, "layernorm: null tensor");
   const mi355_layernorm_args a = *ap;
-  MI355_REQUIRE(a.C > 0 && a.C <= 1024 && a.C % 4 == 0, "layernorm: C must be a multiple of 4 and <= 1024 (got %d)", a.C);
+  MI355_REQUIRE(a.C > 0 && a.C <= 2048 && a.C % 4 == 0, "layernorm: C must be a multiple of 4 and <= 2048 (got %d)", a.C);
   MI355_REQUIRE(a.ldx % 4 == 0 && a.ldy % 4 == 0 && a.x_bstride % 4 == 0 && a.y_bstride % 4 == 0, "layernorm: strides must be multiples of 4");
   MI355_REQUIRE(!a.res || (a.ldr % 4 == 0 && a.res_bstride % 4 == 0), "layernorm: residual strides must be multiples of 4");
   MI355_REQUIRE(a.y_split == 0 || a.y_split == 2 || a.y_split == 4, "layernorm: y_split must be 0, 2 or 4");
   const int64_t rows = (int64_t)a.B * a.L;
   MI355_CLEAR_ERROR();
   const bool vec = ((uintptr_t)a.weight % 16 == 0) && ((uintptr_t)a.bias % 16 == 0) && ((uintptr_t)a.ada_gb % 16 == 0) && (a.ada_ld % 4 == 0);
-  if (vec) hipLaunchKernelGGL(layernorm_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(layernorm_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  if (a.C <= 1024) {
+    if (vec) hipLaunchKernelGGL((layernorm_kernel<true, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((layernorm_kernel<false, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  } else {   // rows of 1025 .. 2048 channels: the same kernel with eight chunks per lane
+    if (vec) hipLaunchKernelGGL((layernorm_kernel<true, 8>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((layernorm_kernel<false, 8>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  }
   MI355_LAUNCH_CHECK("layernorm");
   return MI355_OK;
 }

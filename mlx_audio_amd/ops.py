@@ -972,6 +972,51 @@ def dwconv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], y: to
     return y
 
 
+FSMN_MAX_TAPS = 31  # MI355_FSMN_MAX_TAPS
+FSQ_SCALE = 0.9990000128746033  # FSQCodebook.encode (codec/models/s3/model_v2.py:89)
+
+
+def fsmn_memory(v: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, add: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None):
+    """``y[b, t] = add[b, t] + m(b, t) * (sum_j w[:, j] * m(b, t + j - left) * v[b, t + j - left] + v[b, t])`` (``mi355_fsmn_memory``): the FSMN memory
+    block of the S3 tokenizer's attention.  ``v`` / ``add`` / ``y`` channels-last views [B, L, C] (``v`` may be a third of a fused q|k|v buffer), ``w``
+    [C, K] float32 as ``dwconv`` takes it (K odd, <= ``FSMN_MAX_TAPS``), ``lens`` int32 [B].  ``y`` must not alias ``v``."""
+    B, L, C, vbs, ldv = _nlc(v)
+    By, Ly, Cy, ybs, ldy = _nlc(y)
+    assert (By, Ly, Cy) == (B, L, C)
+    assert w.dim() == 2 and w.shape[0] == C and w.is_contiguous() and w.dtype == torch.float32
+    kw = dict(v=_ptr(v), v_bstride=vbs, ldv=ldv, w=_ptr(w), K=w.shape[1], C=C, L=L, lens=_ptr(lens), B=B, y=_ptr(y), y_bstride=ybs, ldy=ldy)
+    if lens is not None:
+        assert lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous()
+    if add is not None:
+        Ba, La, Ca, abs_, ald = _nlc(add)
+        assert (Ba, La, Ca) == (B, L, C)
+        kw.update(add=_ptr(add), add_bstride=abs_, add_ld=ald)
+    _lib.call_struct("mi355_fsmn_memory", "mi355_fsmn_memory_args", _stream(), **kw)
+    return y
+
+
+def fsq_encode(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], *, lens: Optional[torch.Tensor] = None, return_h: bool = False):
+    """FSQ codes of ``x`` [B, L, C] (rows contiguous over B and L) or [rows, C]: int32 ``sum_d (rint(tanh(h_d) * FSQ_SCALE) + 1) * 3^d`` with
+    ``h = x w^T + b``, ``w`` [8, C], ``b`` [8] (``mi355_fsq_encode``); zero at and beyond ``lens[b]``.  ``return_h`` adds the pre-activations [..., 8]."""
+    assert x.dtype == torch.float32 and x.is_cuda and x.stride(-1) == 1
+    if x.dim() == 3:
+        assert x.stride(0) == x.shape[1] * x.stride(1), "fsq_encode: the rows of a batch must be evenly spaced"
+        lead, L, ldx = (x.shape[0], x.shape[1]), x.shape[1], x.stride(1)
+    else:
+        assert x.dim() == 2 and lens is None
+        lead, L, ldx = (x.shape[0],), 0, x.stride(0)
+    C = x.shape[-1]
+    rows = int(np.prod(lead))
+    assert w.shape == (8, C) and w.is_contiguous() and w.dtype == torch.float32 and (b is None or (b.numel() == 8 and b.is_contiguous() and b.dtype == torch.float32))
+    if lens is not None:
+        assert lens.dtype == torch.int32 and lens.numel() == lead[0] and lens.is_contiguous()
+    codes = torch.empty(lead, dtype=torch.int32, device=x.device)
+    h = torch.empty(lead + (8,), dtype=torch.float32, device=x.device) if return_h else None
+    _lib.call_struct("mi355_fsq_encode", "mi355_fsq_encode_args", _stream(), x=_ptr(x), ldx=ldx, rows=rows, C=C, w=_ptr(w), b=_ptr(b), lens=_ptr(lens), L=L,
+                     codes=_ptr(codes), h=_ptr(h))
+    return (codes, h) if return_h else codes
+
+
 def sample(logits: torch.Tensor, out: torch.Tensor, *, V: Optional[int] = None, suppress_mask=None, history=None, n_hist: int = 0,
            hist_len=None, repetition_penalty: float = 1.0, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
            gumbel=None, done=None, done_token: int = 0, filtered=None):

@@ -143,6 +143,53 @@ def encodec48_encode_lines(args, dev, g, dt16):
                                   f"{'call' if fn is batched else 'chunk'})", 48000, total, 1, wall, dms, conv_roofline(fn), dt16, n * T, n * 4 * T)))
 
 
+def s3_shape_counts(cfg, B, frames):
+    """FLOPs and compulsory HBM bytes of one S3TokenizerV2 pass over B mels of ``frames`` frames, from the shapes: the two stem convs, per block the
+    q|k|v, out and two MLP GEMMs (2 rows 12 n^2), attention (4 B H T^2 dh), the FSMN block (31 taps + 1 add per value), the FSQ head; bytes = every
+    activation operand once (float32) + the fp16 weight images."""
+    na, nm, H, nl = cfg.n_audio_state, cfg.n_mels, cfg.n_audio_head, cfg.n_audio_layer
+    t1 = (frames - 1) // 2 + 1
+    t2 = (t1 - 1) // 2 + 1
+    rows = B * t2
+    gemm = 2.0 * B * t1 * na * 3 * nm + 2.0 * rows * na * 3 * na + nl * 2.0 * rows * 12 * na * na
+    attn = nl * 4.0 * B * H * t2 * t2 * (na // H)
+    fsmn_flops, fsq_flops = nl * 2.0 * rows * na * 32, 2.0 * rows * na * 8
+    fsmn_bytes = nl * 4.0 * rows * na * 3                      # read v, read add, write y
+    act = 4.0 * (B * frames * nm + B * t1 * na * 2 + rows * na * 2) + nl * 4.0 * rows * na * (2 + 2 + 3 + 3 + 1 + 2 + 2 + 2 + 4 + 4 + 4 + 2)
+    weights = 2.0 * (na * 3 * nm + na * 3 * na + nl * 12 * na * na)
+    return dict(gemm_gflop=gemm / 1e9, attention_gflop=attn / 1e9, fsmn_gflop=fsmn_flops / 1e9, fsq_gflop=fsq_flops / 1e9, fsmn_GB=fsmn_bytes / 1e9,
+                compulsory_GB=(act + fsmn_bytes + weights + 4.0 * rows * (na + 1)) / 1e9, code_frames=t2)
+
+
+def s3_encode_lines(args, dev, g, dt16):
+    """S3TokenizerV2 at the published size (1280 / 20 / 6) on seeded weights: 64 clips x 10 s (the voice-prompt batch) and 1 x 30 s, from the mel and
+    from the waveform (fused log-mel kernel included)."""
+    from mlx_audio_amd.codec.models.s3 import ModelConfig, S3TokenizerV2
+    from mlx_audio_amd.frontends import whisper_style_log_mel
+
+    cfg = ModelConfig()
+    eng = S3TokenizerV2("speech_tokenizer_v2_25hz", cfg, device=dev, seed=0)
+    for B, seconds in ((64, 10.0), (1, 30.0)):
+        n = int(seconds * 16000)
+        t = torch.arange(n, dtype=torch.float32) / 16000.0
+        audio = (0.4 * torch.sin(2 * torch.pi * 180 * t) * (0.6 + 0.4 * torch.sin(2 * torch.pi * 3 * t)))[None] + 0.1 * torch.randn(B, n, generator=g)
+        audio = audio.to(dev)
+        mel_of = lambda: whisper_style_log_mel(audio, 16000, 400, 160, cfg.n_mels, periodic_window=True, drop_last=False).transpose(1, 2)  # noqa: E731
+        mel = mel_of().contiguous()
+        frames = int(mel.shape[2])
+        lens = [frames] * B
+        counts = s3_shape_counts(cfg, B, frames)
+        for name, fn in (("from the mel", lambda: eng(mel, lens)[0]), ("from the waveform (log-mel included)", lambda: eng(mel_of(), lens)[0])):
+            out, wall, dms = timed(fn, args.steps, args.warmup)
+            d = enc_line(f"S3 tokenizer v2 (s3_v2: 1280 wide, 20 heads, 6 FSMN attention blocks, FSQ 3^8), {name}",
+                         f"{B} x {seconds:g} s of 16 kHz audio = {frames} mel frames -> {int(out.shape[1])} codes of 25 Hz", 16000, n, B, wall, dms, conv_roofline(fn), dt16,
+                         int(out.shape[1]), int(out.shape[1]))
+            total_tflop = (counts["gemm_gflop"] + counts["attention_gflop"] + counts["fsmn_gflop"] + counts["fsq_gflop"]) / 1e3
+            d["s3_counts"] = dict(counts, achieved_TFLOPs=total_tflop / (dms * 1e-3), frac_of_mfma_peak=total_tflop / (dms * 1e-3) / MFMA_PEAK_TFLOPS,
+                                  compulsory_GBps=counts["compulsory_GB"] / (dms * 1e-3))
+            print(json.dumps(d))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -150,7 +197,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default="")
-    ap.add_argument("--encode", action="store_true", help="the ENCODE lines instead (round 5): DAC / SNAC / EnCodec waveform -> codes (encoder + residual codebook search)")
+    ap.add_argument("--encode", action="store_true", help="the ENCODE lines instead (round 5): DAC / SNAC / EnCodec waveform -> codes (encoder + residual codebook search); ``--only s3_v2``: the S3 tokenizer")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     B = args.batch
@@ -160,6 +207,8 @@ def main():
     if args.encode:
         if args.only in ("", "encodec48"):
             encodec48_encode_lines(args, dev, g, dt16)
+        if args.only in ("", "s3_v2"):
+            s3_encode_lines(args, dev, g, dt16)
         return encode_lines(args, dev, g, dt16)
 
     if args.only in ("", "encodec48"):
