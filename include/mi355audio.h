@@ -1010,6 +1010,55 @@ int mi355_stack_decode_step(const mi355_stack_desc* d, float* x, int32_t B, int3
 /* bytes of mi355_stack_desc.rows_ws a step of B (9..64) sequences needs (planes of the three GEMM inputs + the largest set of partial slabs) */
 int64_t mi355_stack_rows_ws_bytes(const mi355_stack_desc* d, int32_t B);
 
+/* ------------------------------------------------------------------------------------------
+ * Whisper word-level timestamps (stt/models/whisper/timing.py:111-181): cross-attention alignment weights, the standardise / median / head-mean
+ * matrix and the dynamic-time-warping path, all on the device (align.hip).  Every kernel takes B items with per-item lengths; nothing is read
+ * or written beyond an item's own lengths.  The library allocates nothing.
+ *
+ * mi355_align_qk_softmax: w[b, slot, t, f] = softmax over f of (qk_scale * scale * q[b, t, head] . k[b, f, head]), float32, for the n_pairs
+ * (head, slot) pairs of one decoder layer.  q [B, T, ldq] float32, head h at columns [h*dh, (h+1)*dh); k as in mi355_flash_attn_args (rows: head h
+ * at element h*dh of a row, rows ldk apart; k_hstride != 0: head-major planes), element type kv_dtype (MI355_KV_*), strides in elements; dh 64 or 128.
+ * lens_t / lens_f nullable (then T / F).  w is [B, A, Tmax, Fmax] with the strides given (floats). */
+typedef struct {
+  const float* q; int64_t q_bstride; int32_t ldq;
+  const void* k; int64_t k_bstride; int64_t k_hstride; int32_t ldk; int32_t kv_dtype;
+  int32_t dh; int32_t B; int32_t T; int32_t F;
+  const int32_t* lens_t; const int32_t* lens_f;
+  const int32_t* pairs; int32_t n_pairs;      /* device int32 [n_pairs, 2]: (head, slot) */
+  int32_t heads;                              /* heads per q row (validates nothing on the device: every pair's head must be < heads) */
+  float scale; float qk_scale;
+  float* w; int64_t w_bstride; int64_t w_astride; int32_t ldw; int32_t A;   /* w[b, slot, t, f] at b*w_bstride + slot*w_astride + t*ldw + f; slot < A */
+} mi355_align_qk_args;
+int mi355_align_qk_softmax(const mi355_align_qk_args* a, void* stream);
+
+/* mi355_align_matrix (timing.py:148-154): per (head, frame) the mean and population standard deviation over the lens_t[b] tokens, (w - mean) / std
+ * (IEEE division), a median filter of odd width medfilt_width (<= 15) along the frames with reflect padding (values pass unfiltered when
+ * F <= medfilt_width / 2), the mean over the A heads, token rows [row_begin, lens_t[b] - row_trim) kept, and out[b, n, f] = (negate ? -1 : 1) * that.
+ * standardize = 0 skips the statistics (a plain median filter when A = 1).  stats: caller's scratch of B * A * F * 2 floats (unused when standardize = 0). */
+typedef struct {
+  const float* w; int64_t w_bstride; int64_t w_astride; int32_t ldw; int32_t A;
+  int32_t B; int32_t T; int32_t F; const int32_t* lens_t; const int32_t* lens_f;
+  int32_t medfilt_width; int32_t standardize; int32_t negate; int32_t row_begin; int32_t row_trim;
+  float* stats;
+  float* out; int64_t out_bstride; int32_t ldo;
+} mi355_align_matrix_args;
+int mi355_align_matrix(const mi355_align_matrix_args* a, void* stream);
+
+/* mi355_dtw (timing.py:52-99): cost [B, N, ldc] float32 with lens_n[b] x lens_m[b] valid cells per item (nullable: N x M) -> the warping path in forward
+ * order, text_idx[b, 0:path_len[b]] / time_idx[b, ...] (int32, items path_cap >= N + M apart).  float32 accumulation, one add per cell, the reference's
+ * comparison chain and border handling: given the same input the path is the reference's bit for bit.  N <= 1024.  ws: mi355_dtw_ws_bytes(N, M, B) bytes. */
+typedef struct {
+  const float* cost; int64_t cost_bstride; int32_t ldc;
+  int32_t B; int32_t N; int32_t M; const int32_t* lens_n; const int32_t* lens_m;
+  int32_t* text_idx; int32_t* time_idx; int32_t path_cap; int32_t* path_len;
+  void* ws; int64_t ws_bytes;
+} mi355_dtw_args;
+int mi355_dtw(const mi355_dtw_args* a, void* stream);
+int64_t mi355_dtw_ws_bytes(int32_t N, int32_t M, int32_t B);
+
+/* out[r] = softmax(logits[r, 0:V])[tokens[r]] with a per-row token id (timing.py:135-139); a token outside [0, V) gives 0 without a read. */
+int mi355_softmax_prob_rows(const float* logits, int64_t ld, int32_t V, int32_t R, const int32_t* tokens, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -897,6 +897,92 @@ def softmax_prob_at(logits: torch.Tensor, token: int, V: Optional[int] = None) -
     return out
 
 
+# --------------------------------------------------------------------------------------- Whisper word-level timestamps (align.hip)
+def softmax_prob_rows(logits: torch.Tensor, tokens: torch.Tensor, V: Optional[int] = None) -> torch.Tensor:
+    """out[r] = softmax(logits[r, :V])[tokens[r]] (timing.py:135-139): the per-row sibling of ``softmax_prob_at``."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.float32
+    assert tokens.dtype == torch.int32 and tokens.dim() == 1 and tokens.is_contiguous() and tokens.numel() == logits.shape[0]
+    out = torch.empty((logits.shape[0],), dtype=torch.float32, device=logits.device)
+    lib = _lib.load()
+    rc = lib.mi355_softmax_prob_rows(_ptr(logits), logits.stride(0), V or logits.shape[1], logits.shape[0], _ptr(tokens), _ptr(out), _stream())
+    _lib.check(rc, "mi355_softmax_prob_rows")
+    return out
+
+
+def align_qk_softmax(q: torch.Tensor, k: torch.Tensor, w: torch.Tensor, pairs: torch.Tensor, *, heads: int, dh: int, scale: Optional[float] = None,
+                     qk_scale: float = 1.0, lens_t=None, lens_f=None, head_major: bool = False, F: Optional[int] = None) -> torch.Tensor:
+    """w[b, slot, t, f] = softmax_f(qk_scale * scale * q[b, t, head] . k[b, f, head]) for the ``pairs`` [n, 2] = (head, slot) of one decoder
+    layer (a host list, range-checked here, or an int32 device tensor the CALLER has checked: the kernel trusts it).  q [B, T, >= heads * dh] float32; k rows [B, Tk, >= heads * dh] or head-major [B, heads, Tk, dh] (float32 / bfloat16 / float16) as
+    ``flash_attention`` takes them; w float32 [B, A, Tmax, Fmax] (last stride 1).  Keys 0 .. F (default: all Tk), cut per item by ``lens_f``."""
+    B, T, _, qbs, ldq = _nlc(q)
+    khs = 0
+    if head_major:
+        assert k.dim() == 4 and k.stride(3) == 1
+        Tk, kbs, khs, ldk = k.shape[2], k.stride(0), k.stride(1), k.stride(2)
+    else:
+        assert k.dim() == 3 and k.stride(2) == 1
+        Tk, kbs, ldk = k.shape[1], k.stride(0), k.stride(1)
+    assert k.is_cuda and k.shape[0] == B and k.dtype in KV_DTYPES
+    assert w.dim() == 4 and w.dtype == torch.float32 and w.is_cuda and w.stride(3) == 1 and w.shape[0] == B
+    if not isinstance(pairs, torch.Tensor):   # a host list is checked here: the device validates neither the heads nor the slots
+        assert len(pairs) > 0 and all(0 <= int(h) < heads and 0 <= int(sl) < w.shape[1] for h, sl in pairs), "align_qk_softmax: (head, slot) out of range"
+        pairs = torch.tensor([[int(h), int(sl)] for h, sl in pairs], dtype=torch.int32, device=q.device)
+    assert pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous() and pairs.is_cuda
+    F = Tk if F is None else F
+    assert 0 < F <= Tk and T <= w.shape[2] and F <= w.shape[3]
+    _lib.call_struct("mi355_align_qk_softmax", "mi355_align_qk_args", _stream(), q=_ptr(q), q_bstride=qbs, ldq=ldq, k=_ptr(k), k_bstride=kbs,
+                     k_hstride=khs, ldk=ldk, kv_dtype=KV_DTYPES[k.dtype], dh=dh, B=B, T=T, F=F, lens_t=_ptr(lens_t), lens_f=_ptr(lens_f),
+                     pairs=_ptr(pairs), n_pairs=pairs.shape[0], heads=heads, scale=(1.0 / math.sqrt(dh)) if scale is None else scale,
+                     qk_scale=qk_scale, w=_ptr(w), w_bstride=w.stride(0), w_astride=w.stride(1), ldw=w.stride(2), A=w.shape[1])
+    return w
+
+
+def align_matrix(w: torch.Tensor, out: torch.Tensor, *, T: Optional[int] = None, F: Optional[int] = None, lens_t=None, lens_f=None,
+                 medfilt_width: int = 7, standardize: bool = True, negate: bool = True, row_begin: int = 0, row_trim: int = 1,
+                 stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """timing.py:148-154 on w [B, A, T, F]: standardise over the tokens, median filter over the frames (reflect padding), mean over the A heads;
+    out[b, n, f] = -(that) for the token rows ``row_begin <= t < lens_t[b] - row_trim``.  ``standardize=False, negate=False, row_trim=0`` on one head
+    is the plain median filter."""
+    assert w.dim() == 4 and w.dtype == torch.float32 and w.is_cuda and w.stride(3) == 1
+    assert out.dim() == 3 and out.dtype == torch.float32 and out.is_cuda and out.stride(2) == 1 and out.shape[0] == w.shape[0]
+    B, A = w.shape[0], w.shape[1]
+    T = w.shape[2] if T is None else T
+    F = w.shape[3] if F is None else F
+    assert T <= w.shape[2] and F <= w.shape[3] and F <= out.shape[2] and T - row_trim - row_begin <= out.shape[1]
+    if standardize and stats is None:
+        stats = torch.empty(B * A * F * 2, dtype=torch.float32, device=w.device)
+    _lib.call_struct("mi355_align_matrix", "mi355_align_matrix_args", _stream(), w=_ptr(w), w_bstride=w.stride(0), w_astride=w.stride(1), ldw=w.stride(2),
+                     A=A, B=B, T=T, F=F, lens_t=_ptr(lens_t), lens_f=_ptr(lens_f), medfilt_width=medfilt_width, standardize=int(standardize),
+                     negate=int(negate), row_begin=row_begin, row_trim=row_trim, stats=_ptr(stats), out=_ptr(out), out_bstride=out.stride(0),
+                     ldo=out.stride(1))
+    return out
+
+
+def dtw_workspace_bytes(N: int, M: int, B: int) -> int:
+    return int(_lib.load().mi355_dtw_ws_bytes(N, M, B))
+
+
+def dtw(cost: torch.Tensor, *, N: Optional[int] = None, M: Optional[int] = None, lens_n=None, lens_m=None, ws: Optional[torch.Tensor] = None):
+    """timing.py:52-99 on cost [B, N, M] float32 (per-item sizes ``lens_n`` / ``lens_m``): (text_idx, time_idx int32 [B, N + M], path_len int32 [B]),
+    the warping path in forward order -- given the same float32 input, the reference's path bit for bit.  N <= 1024."""
+    assert cost.dim() == 3 and cost.dtype == torch.float32 and cost.is_cuda and cost.stride(2) == 1
+    B = cost.shape[0]
+    N = cost.shape[1] if N is None else N
+    M = cost.shape[2] if M is None else M
+    assert N <= cost.shape[1] and M <= cost.shape[2]
+    cap = N + M
+    text = torch.empty((B, cap), dtype=torch.int32, device=cost.device)
+    time = torch.empty((B, cap), dtype=torch.int32, device=cost.device)
+    plen = torch.zeros((B,), dtype=torch.int32, device=cost.device)
+    need = dtw_workspace_bytes(N, M, B)
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=cost.device)
+    _lib.call_struct("mi355_dtw", "mi355_dtw_args", _stream(), cost=_ptr(cost), cost_bstride=cost.stride(0), ldc=cost.stride(1), B=B, N=N, M=M,
+                     lens_n=_ptr(lens_n), lens_m=_ptr(lens_m), text_idx=_ptr(text), time_idx=_ptr(time), path_cap=cap, path_len=_ptr(plen),
+                     ws=_ptr(ws), ws_bytes=ws.numel() * ws.element_size())
+    return text, time, plen
+
+
 def rmsnorm(x: torch.Tensor, y: torch.Tensor, weight: Optional[torch.Tensor], eps: float = 1e-6, lens=None):
     B, L, C, xbs, ldx = _nlc(x)
     _, _, _, ybs, ldy = _nlc(y)

@@ -71,7 +71,7 @@ def sinusoids(length: int, channels: int, max_timescale: float = 10000) -> torch
 
 class WhisperEngine:
     def __init__(self, weights: Dict[str, torch.Tensor], dims: ModelDimensions, device: str = "cuda:0", precision: int = 4,
-                 kv_dtype: torch.dtype = torch.float16):
+                 kv_dtype: torch.dtype = torch.float16, pos_dtype: torch.dtype = torch.float16):
         ops.require_gpu()
         assert precision in (3, 4)
         assert kv_dtype in ops.KV_DTYPES
@@ -130,7 +130,10 @@ class WhisperEngine:
         wp[:, 1, :na] = w2[:, 1, :]
         wp[:, 1, na:] = w2[:, 2, :]
         self.conv2 = ops.pack_conv(wp, w["encoder.conv2.bias"], dev, f16=True)
-        self.enc_pos = sinusoids(dims.n_audio_ctx, na).to(torch.float16).to(torch.float32).to(dev)[None]  # whisper.py:434 .astype(dtype)
+        # whisper.py:434 .astype(dtype): the sinusoids are rounded to the MODEL's dtype -- fp16 for the published checkpoints (the default); a float32
+        # model (``pos_dtype=torch.float32``) keeps them as computed.  The rounding is half an fp16 ulp, up to 2.4e-4 on entries near 1
+        assert pos_dtype in (torch.float16, torch.bfloat16, torch.float32)
+        self.enc_pos = sinusoids(dims.n_audio_ctx, na).to(pos_dtype).to(torch.float32).to(dev)[None]
         self.enc_blocks = [block(f"encoder.blocks.{i}", na, False) for i in range(dims.n_audio_layer)]
         self.ln_post = ln("encoder.ln_post")
         self.tok_emb = w["decoder.token_embedding.weight"].to(dev)
@@ -295,8 +298,9 @@ class WhisperEngine:
             t = self._tile_images[id(l)] = ops.tiles16_from_rowmajor(l.rm)
         return t
 
-    def decoder_step(self, tokens: torch.Tensor, st: dict) -> torch.Tensor:
-        """tokens int32 [B, n] (device view) appended at offset st['n'] -> final-LN hidden states [B, n, n_text_state]."""
+    def decoder_step(self, tokens: torch.Tensor, st: dict, cross_hook=None) -> torch.Tensor:
+        """tokens int32 [B, n] (device view) appended at offset st['n'] -> final-LN hidden states [B, n, n_text_state].  ``cross_hook(layer, q)`` (the
+        alignment pass) sees each layer's cross-attention queries before they are consumed."""
         d = self.dims
         B, n = tokens.shape
         off = st["n"]
@@ -304,7 +308,7 @@ class WhisperEngine:
         nt, H, dh = d.n_text_state, d.n_text_head, self.dh
         x = self._f(B, n, nt)
         ops.gather_rows(self.tok_emb, tokens, x, pos_table=self.pos_emb[off:off + n])
-        if n == 1 and B <= 64 and self.native_decode:  # the whole 12-layer step from the native runner: one call instead of ~100 launches from Python
+        if n == 1 and B <= 64 and self.native_decode and cross_hook is None:  # the whole 12-layer step from the native runner: one call instead of ~100 launches from Python
             nd = self._native_desc(st)
             ws = self._f(B * (2 * nt + 4 * nt + 2 * nt))
             out = self._f(B, 1, nt)
@@ -326,6 +330,8 @@ class WhisperEngine:
             ops.flash_attention(q, cache[:, :off + n, 0:nt], cache[:, :off + n, nt:], att, heads=H, dh=dh, scale=dh ** -0.5, causal=True)
             self._linear(att, blk.out, x, res=x)
             self._linear(x, blk.cq, q, ln=blk.cross_ln)
+            if cross_hook is not None:
+                cross_hook(i, q)
             ops.flash_attention(q, st["cross_k"][i], st["cross_v"][i], att, heads=H, dh=dh, scale=dh ** -0.5, head_major=True)
             self._linear(att, blk.cout, x, res=x)
             self._linear(x, blk.mlp1, mid, post_act=ACT_GELU, ln=blk.mlp_ln)
@@ -351,6 +357,67 @@ class WhisperEngine:
             ops.rows_gemm(planes, self._tiles(self.logits_lin), out.view(1, B, vp), B, R, kgroups=1)
             return out
         self._linear(hidden, self.logits_lin, out[:, :, :self.dims.n_vocab])
+        return out
+
+    # ------------------------------------------------------------------ word-level alignment (timing.py:111-155)
+    def align(self, xa: torch.Tensor, tokens: Sequence[Sequence[int]], num_frames: Sequence[int], heads: Sequence[Sequence[int]], *, sot_len: int,
+              eot: int, medfilt_width: int = 7, qk_scale: float = 1.0, return_matrix: bool = False):
+        """One teacher-forced decoder pass per window over ``tokens[b]`` = ``[*sot_sequence, no_timestamps, *text_tokens, eot]``; the cross-attention
+        probabilities of the alignment ``heads`` [(layer, head)] over the first ``num_frames[b] // 2`` encoder frames, standardised over tokens,
+        median-filtered over frames and averaged over heads, then the DTW path through the negated matrix -- all on the device.  Returns one
+        ``(text_indices, time_indices, text_token_probs)`` triple of numpy arrays per window; the path and the probabilities are the only thing that
+        crosses to the host (``return_matrix``: also the device tensor [B, N, F] and the per-item (N, F), for tests)."""
+        d = self.dims
+        dev = self.device
+        B = len(tokens)
+        assert B == xa.shape[0] == len(num_frames) and B > 0
+        lens = [len(t) for t in tokens]
+        Tmax = max(lens)
+        assert min(lens) >= sot_len + 3, "an alignment pass needs at least one text token"
+        assert Tmax <= d.n_text_ctx
+        nf = [min(int(f) // 2, d.n_audio_ctx) for f in num_frames]
+        assert min(nf) > 0
+        Fmax = max(nf)
+        heads = [(int(l), int(h)) for l, h in heads]
+        assert heads and all(0 <= l < d.n_text_layer and 0 <= h < d.n_text_head for l, h in heads)
+        A = len(heads)
+        tk = np.full((B, Tmax), eot, dtype=np.int32)
+        nxt = np.full((B, Tmax), -1, dtype=np.int32)    # the token each position's logits are asked about (-1: none)
+        for b, t in enumerate(tokens):
+            tk[b, :len(t)] = t
+            nxt[b, sot_len:len(t) - 2] = t[sot_len + 1:len(t) - 1]
+        host = torch.from_numpy(np.concatenate([tk.reshape(-1), nxt.reshape(-1), np.asarray(lens, np.int32), np.asarray(nf, np.int32),
+                                               np.asarray([n - sot_len - 1 for n in lens], np.int32)])).to(dev)
+        tk_d, nxt_d = host[:B * Tmax].view(B, Tmax), host[B * Tmax:2 * B * Tmax]
+        lens_t, lens_f, lens_n = host[2 * B * Tmax:2 * B * Tmax + B], host[2 * B * Tmax + B:2 * B * Tmax + 2 * B], host[2 * B * Tmax + 2 * B:]
+        per_layer: Dict[int, torch.Tensor] = {}
+        for l in sorted({l for l, _ in heads}):
+            per_layer[l] = torch.tensor([[h, s] for s, (ll, h) in enumerate(heads) if ll == l], dtype=torch.int32, device=dev)   # h < n_text_head, s < A: checked above
+        w = self._f(B, A, Tmax, Fmax)
+        st = self.new_state(xa.to(dev, torch.float32))
+
+        def hook(i, q):
+            pairs = per_layer.get(i)
+            if pairs is not None:
+                ops.align_qk_softmax(q, st["cross_k"][i], w, pairs, heads=d.n_text_head, dh=self.dh, scale=self.dh ** -0.5, qk_scale=qk_scale,
+                                     lens_t=lens_t, lens_f=lens_f, head_major=True, F=Fmax)
+
+        hid = self.decoder_step(tk_d, st, cross_hook=hook)
+        lg = self.logits(hid)
+        probs = ops.softmax_prob_rows(lg.view(B * Tmax, lg.shape[2]), nxt_d, V=eot)
+        Nmax = Tmax - sot_len - 1
+        cost = self._f(B, Nmax, Fmax)
+        ops.align_matrix(w, cost, T=Tmax, F=Fmax, lens_t=lens_t, lens_f=lens_f, medfilt_width=medfilt_width, row_begin=sot_len, row_trim=1)
+        text, time, plen = ops.dtw(cost, N=Nmax, M=Fmax, lens_n=lens_n, lens_m=lens_f)
+        packed = torch.cat([text, time, plen[:, None], probs.view(B, Tmax).view(torch.int32)], dim=1).cpu().numpy()   # the one device-to-host copy
+        cap = Nmax + Fmax
+        out = []
+        for b in range(B):
+            L = int(packed[b, 2 * cap])
+            pr = packed[b, 2 * cap + 1:].view(np.float32)[sot_len:lens[b] - 2]
+            out.append((packed[b, :L].astype(np.int64), packed[b, cap:cap + L].astype(np.int64), pr.copy()))
+        if return_matrix:
+            return out, cost, [(lens[b] - sot_len - 1, nf[b]) for b in range(B)]
         return out
 
     # ------------------------------------------------------------------ decode loop (decoding.py:588-632)

@@ -77,6 +77,58 @@ class Tokenizer:
             return self.codec.decode(toks)
         return "".join(f"<|{t}|>" for t in toks)
 
+    def _need_codec(self):
+        if self.codec is None:
+            raise RuntimeError("no vocabulary available: pass codec= (tiktoken Encoding / HF tokenizer) to Tokenizer")
+        return self.codec
+
+    def decode_with_timestamps(self, tokens, **kwargs) -> str:
+        """whisper.py:84-88: every id goes to the vocabulary object, timestamp tokens included."""
+        if hasattr(tokens, "tolist"):
+            tokens = tokens.tolist()
+        return self._need_codec().decode([int(t) for t in tokens])
+
+    def split_to_word_tokens(self, tokens):
+        """whisper.py:194-198: (words, token groups); languages written without spaces split at unicode boundaries only."""
+        self._need_codec()
+        if self.language in {"zh", "ja", "th", "lo", "my", "yue"}:
+            return self._split_tokens_on_unicode(tokens)
+        return self._split_tokens_on_spaces(tokens)
+
+    def _split_tokens_on_unicode(self, tokens):
+        """whisper.py:200-224: a group closes once its text decodes without a dangling replacement character."""
+        decoded_full = self.decode_with_timestamps(tokens)
+        replacement_char = "\ufffd"
+        words, word_tokens, current_tokens = [], [], []
+        unicode_offset = 0
+        for token in tokens:
+            current_tokens.append(token)
+            decoded = self.decode_with_timestamps(current_tokens)
+            if replacement_char not in decoded or decoded_full[unicode_offset + decoded.index(replacement_char)] == replacement_char:
+                words.append(decoded)
+                word_tokens.append(current_tokens)
+                current_tokens = []
+                unicode_offset += len(decoded)
+        return words, word_tokens
+
+    def _split_tokens_on_spaces(self, tokens):
+        """whisper.py:226-245: unicode groups joined into words at leading spaces, punctuation and special tokens."""
+        import string
+
+        subwords, subword_tokens_list = self._split_tokens_on_unicode(tokens)
+        words, word_tokens = [], []
+        for subword, subword_tokens in zip(subwords, subword_tokens_list):
+            special = subword_tokens[0] >= self.eot
+            with_space = subword.startswith(" ")
+            punctuation = subword.strip() in string.punctuation
+            if special or with_space or punctuation or len(words) == 0:
+                words.append(subword)
+                word_tokens.append(subword_tokens)
+            else:
+                words[-1] = words[-1] + subword
+                word_tokens[-1].extend(subword_tokens)
+        return words, word_tokens
+
 
 def get_tokenizer(multilingual: bool, *, num_languages: int = 99, language: Optional[str] = None, task: Optional[str] = None,
                   codec=None) -> Tokenizer:

@@ -10,15 +10,21 @@ and its ``DecodingResult``, ``generate(audio, *, language, task, temperature, ..
 ``generate`` follows the reference's window loop: each 30 s window holds only its own frames (zero-padded in the log-mel domain),
 temperature fallback over the ``temperature`` tuple (sampling = arg-max of ``logits / T`` + device Gumbel noise in the decode-rules kernel,
 ``best_of`` groups ranked like ``MaximumLikelihoodRanker``), prompt conditioning on the previous windows / ``initial_prompt`` / ``hotwords``,
-``clip_timestamps``, segment cutting at consecutive timestamps.
+``clip_timestamps``, segment cutting at consecutive timestamps, and -- with weights loaded -- ``word_timestamps`` / ``hallucination_silence_threshold``
+(whisper.py:1170-1260): each window's text is aligned to its audio by ``timing.add_word_timestamps``, whose cross-attention weights, median filter and
+DTW run on the device (``WhisperEngine.align``), ``seek`` follows the last word's end and silence around anomalous segments is skipped.  The alignment
+has no host implementation, so a ``Model`` without an engine raises ``NotImplementedError`` for these two options before anything is decoded.
 
-Deliberately not carried over (host front/back ends): resampling of non-16 kHz files, word-level timestamps and
-``hallucination_silence_threshold`` (DTW over cross-attention weights), streaming (AlignAtt) -- these raise ``NotImplementedError``.
+Deliberately not carried over (host front/back ends): resampling of non-16 kHz files and streaming (AlignAtt), which raises
+``NotImplementedError``.
 ``detect_language`` returns the reference's (language tokens, probability dicts) pair.
 """
 from __future__ import annotations
 
+import base64
+import gzip
 import time
+import warnings
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple, Union
 
@@ -30,6 +36,7 @@ from .audio import FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RA
 from .decoding import DecodingOptions, DecodingResult
 from .decoding import decode as decode_function
 from .synthetic import ModelDimensions
+from .timing import add_word_timestamps
 from .tokenizer import LANGUAGES, get_tokenizer
 
 ModelConfig = ModelDimensions  # alias used by load_model (whisper.py:325)
@@ -64,6 +71,40 @@ def _filter_decode_options(decode_options: dict) -> dict:
     return {k: v for k, v in decode_options.items() if k in _DECODING_OPTION_NAMES}
 
 
+def _get_end(segments: List[dict]) -> Optional[float]:
+    """whisper.py:265-269: the end of the last word, else of the last segment."""
+    return next((w["end"] for s in reversed(segments) for w in reversed(s["words"])), segments[-1]["end"] if segments else None)
+
+
+def word_anomaly_score(word: dict) -> float:
+    """whisper.py:1075-1085: anomalous words are very long, very short or improbable."""
+    probability = word.get("probability", 0.0)
+    duration = word["end"] - word["start"]
+    score = 0.0
+    if probability < 0.15:
+        score += 1.0
+    if duration < 0.133:
+        score += (0.133 - duration) * 15
+    if duration > 2.0:
+        score += duration - 2.0
+    return score
+
+
+def is_segment_anomaly(segment: Optional[dict], punctuation: str) -> bool:
+    """whisper.py:1087-1095."""
+    if segment is None or not segment["words"]:
+        return False
+    words = [w for w in segment["words"] if w["word"] not in punctuation]
+    words = words[:8]
+    score = sum(word_anomaly_score(w) for w in words)
+    return score >= 3 or score + 0.01 >= len(words)
+
+
+def next_words_segment(segments: List[dict]) -> Optional[dict]:
+    """whisper.py:1097-1098."""
+    return next((s for s in segments if s["words"]), None)
+
+
 class Model:
     def __init__(self, dims: ModelDimensions, dtype: torch.dtype = torch.float16, device: str = "cuda", precision: int = 4):
         self.dims = dims
@@ -73,6 +114,27 @@ class Model:
         self.engine = None
         self.model_path = None
         self.codec = None  # optional vocabulary object (encode / decode)
+        # whisper.py:522-528: the last half of the decoder layers aligns text to time by default (see set_alignment_heads)
+        all_heads = np.zeros((dims.n_text_layer, dims.n_text_head), dtype=bool)
+        all_heads[dims.n_text_layer // 2:] = True
+        self._alignment_heads = np.asarray(all_heads.nonzero()).T
+
+    @property
+    def alignment_heads(self) -> np.ndarray:
+        """[n, 2] (decoder layer, head) pairs whose cross-attention is used for word timing (whisper.py:530-532)."""
+        return self._alignment_heads
+
+    def set_alignment_heads(self, dump):
+        """whisper.py:534-549: a list / array of (layer, head) pairs, or the base85 + gzip dump of a boolean [n_text_layer, n_text_head] mask."""
+        if isinstance(dump, (list, np.ndarray)):
+            self._alignment_heads = np.asarray(dump)
+        elif isinstance(dump, bytes):
+            array = np.frombuffer(gzip.decompress(base64.b85decode(dump)), dtype=bool).copy()
+            mask = array.reshape(self.dims.n_text_layer, self.dims.n_text_head)
+            self._alignment_heads = np.asarray(mask.nonzero()).T
+        else:
+            raise ValueError(f"Invalid type for `dump`: {type(dump)}. Expected a list, np.ndarray or base85-encoded bytes containing"
+                             " alignment_head information")
 
     # ------------------------------------------------------------------ checkpoint handling
     def sanitize(self, weights: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -106,10 +168,11 @@ class Model:
             # the K / V caches live in the checkpoint's floating dtype like the reference's (whisper.py:360-361): fp16 -> fp16, bf16 -> bf16, fp32 -> fp32
             fdt = [v.dtype for v in w.values() if v.is_floating_point()]
             kv_dtype = max(set(fdt), key=fdt.count) if fdt else torch.float16
+            # ... and so does the encoder's sinusoid table (whisper.py:434 .astype(dtype)): a float32 model keeps it unrounded
             if kv_dtype not in (torch.float16, torch.bfloat16, torch.float32):
                 kv_dtype = torch.float32
             self.engine = WhisperEngine({k: v.to(torch.float32) for k, v in w.items() if v.is_floating_point()}, self.dims,
-                                        device=self.device, precision=self.precision, kv_dtype=kv_dtype)
+                                        device=self.device, precision=self.precision, kv_dtype=kv_dtype, pos_dtype=kv_dtype)
         except KeyError as e:
             raise ValueError(f"Whisper checkpoint is missing parameter {e}") from e
         return self
@@ -192,13 +255,18 @@ class Model:
                  initial_prompt: Optional[str] = None, return_timestamps: bool = True, word_timestamps: bool = False,
                  clip_timestamps: Union[str, List[float]] = "0", hallucination_silence_threshold: Optional[float] = None,
                  hotwords: Optional[List[str]] = None, stream: bool = False, generator: Optional[torch.Generator] = None,
+                 prepend_punctuations: str = "\"'\u201c\u00bf([{-", append_punctuations: str = "\"'.\u3002,\uff0c!\uff01?\uff1f:\uff1a\u201d)]}\u3001",
                  **decode_options) -> STTOutput:
-        """whisper.py:799-1320.  Windows, temperature fallback, prompt conditioning and segment cutting follow the reference; the options that
-        need word-level alignment (``word_timestamps``, ``hallucination_silence_threshold``) and ``stream`` raise instead of being ignored."""
-        if word_timestamps or hallucination_silence_threshold is not None:
-            raise NotImplementedError("word_timestamps / hallucination_silence_threshold (DTW over cross-attention) are outside the MI355X hot path")
+        """whisper.py:799-1320.  Windows, temperature fallback, prompt conditioning, segment cutting, word timestamps and the hallucination / silence
+        skipping follow the reference.  Word-level alignment runs on the device engine only: without one, ``word_timestamps`` and
+        ``hallucination_silence_threshold`` raise instead of being ignored or computed on the host; so does ``stream``."""
+        if (word_timestamps or hallucination_silence_threshold is not None) and self.engine is None:
+            raise NotImplementedError("word_timestamps / hallucination_silence_threshold need the cross-attention alignment and DTW, which run on the "
+                                      "device engine only (there is no host implementation): call load_weights() first")
         if stream:
             raise NotImplementedError("generate(stream=True) is outside the MI355X hot path")
+        if word_timestamps:  # whisper.py:906-908
+            return_timestamps = True
         t_start = time.time()
         if hotwords:  # stt/utils.py:15-34: the vocabulary list is folded into the prompt
             terms = ", ".join(str(t).strip() for t in hotwords if t is not None and str(t).strip())
@@ -207,6 +275,7 @@ class Model:
         decode_options = _filter_decode_options(decode_options)
         decode_options["without_timestamps"] = not return_timestamps
         mel, content_frames = self._prepare_audio(audio)
+        content_duration = float(content_frames * HOP_LENGTH / SAMPLE_RATE)
         if language is None:
             if not self.is_multilingual:
                 language = "en"
@@ -227,6 +296,9 @@ class Model:
         else:
             seek_points[-1] = min(content_frames, seek_points[-1])
         seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
+        punctuation = "\"'\u201c\u00bf([{-\"'.\u3002,\uff0c!\uff01?\uff1f:\uff1a\u201d)]}\u3001"
+        if word_timestamps and task == "translate":  # whisper.py:954-955
+            warnings.warn("Word-level timestamps on translations may not be reliable.")
 
         def decode_with_fallback(segment: torch.Tensor) -> DecodingResult:
             """whisper.py:957-996: retry at the next temperature while the text is too repetitive or too unlikely, unless it is silence."""
@@ -261,9 +333,11 @@ class Model:
             initial_prompt_tokens = list(tokenizer.encode(" " + initial_prompt.strip()))
             all_tokens.extend(initial_prompt_tokens)
         seek = seek_clips[0][0]
+        last_speech_timestamp = 0.0
         for _, seek_clip_end in seek_clips:
             while seek < seek_clip_end:
                 time_offset = float(seek * HOP_LENGTH / SAMPLE_RATE)
+                window_end_time = float((seek + N_FRAMES) * HOP_LENGTH / SAMPLE_RATE)
                 segment_size = min(N_FRAMES, content_frames - seek, seek_clip_end - seek)
                 # whisper.py:1046-1050: only THIS window's frames, padded with 0.0 in the log-mel domain (not the audio that follows)
                 seg = pad_or_trim(mel[seek:seek + segment_size], N_FRAMES, axis=-2)
@@ -277,6 +351,8 @@ class Model:
                     if should_skip:
                         seek += segment_size  # silent window (whisper.py:1056-1069)
                         continue
+                previous_seek = seek
+                segment_duration = segment_size * HOP_LENGTH / SAMPLE_RATE
                 current: List[dict] = []
                 ts = [i for i, t in enumerate(tokens) if t >= tokenizer.timestamp_begin]
                 consecutive = [i for i in range(1, len(tokens))
@@ -307,6 +383,51 @@ class Model:
                         duration = (tokens[ts[-1]] - tokenizer.timestamp_begin) * time_precision
                     current.append(seg_dict(time_offset, time_offset + duration, tokens))
                     seek += segment_size
+                if word_timestamps:  # whisper.py:1170-1188
+                    add_word_timestamps(segments=current, model=self, tokenizer=tokenizer, mel=seg, num_frames=segment_size,
+                                        prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
+                                        last_speech_timestamp=last_speech_timestamp, audio_features=result.audio_features)
+                    if not single_ending:
+                        last_word_end = _get_end(current)
+                        if last_word_end is not None and last_word_end > time_offset:
+                            seek = round(last_word_end * FRAMES_PER_SECOND)
+                    if hallucination_silence_threshold is not None:  # whisper.py:1190-1256: skip silence before possible hallucinations
+                        threshold = hallucination_silence_threshold
+                        if not single_ending:
+                            last_word_end = _get_end(current)
+                            if last_word_end is not None and last_word_end > time_offset:
+                                remaining_duration = window_end_time - last_word_end
+                                seek = round(last_word_end * FRAMES_PER_SECOND) if remaining_duration > threshold else previous_seek + segment_size
+                        # the first segment might be a hallucination: skip the leading silence
+                        first_segment = next_words_segment(current)
+                        if first_segment is not None and is_segment_anomaly(first_segment, punctuation):
+                            gap = first_segment["start"] - time_offset
+                            if gap > threshold:
+                                seek = previous_seek + round(gap * FRAMES_PER_SECOND)
+                                continue
+                        # skip silence before any possible hallucination that is surrounded by silence or more hallucinations
+                        hal_last_end = last_speech_timestamp
+                        for si in range(len(current)):
+                            sgm = current[si]
+                            if not sgm["words"]:
+                                continue
+                            if is_segment_anomaly(sgm, punctuation):
+                                next_segment = next_words_segment(current[si + 1:])
+                                hal_next_start = next_segment["words"][0]["start"] if next_segment is not None else time_offset + segment_duration
+                                silence_before = (sgm["start"] - hal_last_end > threshold or sgm["start"] < threshold
+                                                  or sgm["start"] - time_offset < 2.0)
+                                silence_after = (hal_next_start - sgm["end"] > threshold or is_segment_anomaly(next_segment, punctuation)
+                                                 or window_end_time - sgm["end"] < 2.0)
+                                if silence_before and silence_after:
+                                    seek = round(max(time_offset + 1, sgm["start"]) * FRAMES_PER_SECOND)
+                                    if content_duration - sgm["end"] < threshold:
+                                        seek = content_frames
+                                    current[si:] = []
+                                    break
+                            hal_last_end = sgm["end"]
+                    last_word_end = _get_end(current)  # whisper.py:1258-1260
+                    if last_word_end is not None:
+                        last_speech_timestamp = last_word_end
                 if verbose:
                     for sgm in current:
                         print(f"[{sgm['start']:.3f} --> {sgm['end']:.3f}] {sgm['text']}")
