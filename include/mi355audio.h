@@ -13,7 +13,9 @@
  *   - activations are float32, channels-last: element (b, l, c) of a tensor lives at
  *     base + b*bstride + l*ld + c   (the NLC layout mx.conv1d uses), ld >= C;
  *   - `lens` (nullable) holds the valid row count of every batch item (ragged batches are padded
- *     to a common L; rows >= lens[b] read as zeros and are never written);
+ *     to a common L; rows >= lens[b] read as zeros and are never written).  0 <= lens[b] <= L (T, Lin) is the
+ *     caller's contract: the array lives on the device, so no entry point can check it without a
+ *     synchronisation, and the kernels index rows, and LDS arrays sized by their documented maximum, by it;
  *   - weights are bfloat16 (or float16 for fp16 checkpoints), pre-packed by mi355_pack_* into MFMA fragment order;
  *   - `stream` is a hipStream_t passed as void*; all functions are asynchronous on it;
  *   - return value: 0 = ok, negative = error (text via mi355_last_error()); nothing is allocated,
@@ -357,7 +359,9 @@ int mi355_pack_lstm_wh16_host(const float* wh_fwd_host, const float* wh_bwd_host
  * Multi-head self-attention over short sequences (PL-BERT, T <= 512), fp32.
  * Replaces AlbertSelfAttention's QK^T / softmax / PV (modules.py:493-508).
  * qkv: [B, T, ld] with q at column 0, k at column D, v at 2D (D = heads*dh); keys >= lens[b]
- * get the reference's additive -10000 mask.
+ * get the reference's additive -10000 mask (weight exactly 0 in float32); query rows >= lens[b] of out are not written.
+ * lens[b] <= T (<= 512) is the caller's contract (see Conventions): the probability row in LDS and the value rows are
+ * indexed up to lens[b].
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   const float* qkv; int64_t bstride; int32_t ld;
@@ -396,7 +400,9 @@ int mi355_broadcast_rows(const float* v, int32_t ldv, int32_t C, float* y, int64
 
 /* duration head (kokoro.py:140-147): dur = clip(round(sum_j sigmoid(logits[b,t,j]) / speed), 1, 100),
  * then per item the exclusive scan and the frame->token index (kokoro.py:148-160).
- * frames[b] = sum of durations; idx[b, f] = token of frame f (f < frames[b], up to idx_ld). */
+ * frames[b] = sum of durations (the whole sum, also when it exceeds idx_ld); idx[b, f] = token of frame f (f < frames[b], up to idx_ld:
+ * writes stop at the row end).  T <= 512 is checked; lens[b] <= T is the caller's contract (see Conventions): logits, dur and dur_raw rows
+ * are indexed up to lens[b]. */
 typedef struct {
   const float* logits; int64_t bstride; int32_t ld; int32_t bins;
   int32_t T; const int32_t* lens; int32_t B; float speed;
@@ -531,7 +537,8 @@ typedef struct {
 int mi355_interpolate1d(const mi355_interp1d_args* a, void* stream);
 
 /* Scalar strided conv (1 -> 1 channel, k3, stride 2, pad 1) writing one column of a wider buffer:
- * Decoder.F0_conv / N_conv (istftnet.py:973-974,983-984).  x [B, Lin], y[b, l, col]. */
+ * Decoder.F0_conv / N_conv (istftnet.py:973-974,983-984).  x [B, Lin], y[b, l, col] for l < (lens_in[b] - 1) / 2 + 1; an item with
+ * lens_in[b] = 0 has no output row (nothing is written for it). */
 int mi355_conv1d_c1_k3s2(const float* x, int32_t ldx_b, int32_t Lin, const int32_t* lens_in,
                          float w0, float w1, float w2, float bias, float* y, int64_t y_bstride, int32_t ldy, int32_t col,
                          int32_t Lout, int32_t B, void* stream);

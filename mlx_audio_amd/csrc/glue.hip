@@ -109,7 +109,7 @@ __global__ void conv1d_c1_k3s2_kernel(const float* x, int ldxb, int Lin, const i
   const int l = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
   if (l >= Lout) return;
   const int len = lens_in ? lens_in[b] : Lin;
-  const int lout = (len + 2 - 3) / 2 + 1;
+  const int lout = len > 0 ? (len + 2 - 3) / 2 + 1 : 0;   // an empty item has no output row ((0 - 1) / 2 truncates to 0 in C, which would leave one row of bias)
   if (l >= lout) return;
   const float* xb = x + (int64_t)b * ldxb;
   float s = 0.f;
