@@ -330,6 +330,58 @@ typedef struct {
 int mi355_fsq_encode(const mi355_fsq_encode_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FastConformer encoder (stt/models/parakeet/attention.py, conformer.py): relative-position attention, the fused middle of the
+ * convolution module and the 3 x 3 / stride 2 convs of the dw-striding subsampler.  Three entry points added to ABI 37 (new
+ * structs and functions only; no existing layout changed).  Plain float32, a fixed summation order that does not depend on
+ * the launch geometry: two calls on the same bytes give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+/* RelPositionMultiHeadAttention (attention.py:93-137) behind the projections.  Head h sits at columns [h dh, (h + 1) dh) of
+ * every row.  With n = lens[b] (NULL: T), for i, j < n:
+ *   s_ij = scale * ( (q_i + u_h) . k_j + (q_i + v_h) . p[center - (i - j)] ),   out_i = sum_{j<n} softmax_j(s_i.) v_j;
+ * output rows n <= i < T are written as zeros.  p is the PROJECTED position table [P, ldp], shared by the batch; row center is
+ * distance 0 (rel_shift is out[i, j] = bd[i, T - 1 - i + j], so the row of a pair depends on i - j alone).  dh 64 or 128, T >= 1;
+ * MI355_ERR_ARG without a launch unless 0 <= center - (T - 1) and center + T - 1 < P.  Rows 16-byte aligned (strides multiples of 4).
+ * No [T, T] matrix is written to memory and there is no workspace. */
+typedef struct {
+  const float* q; int64_t q_bstride; int32_t ldq;        /* [B, T, ldq] */
+  const float* k; int64_t k_bstride; int32_t ldk;
+  const float* v; int64_t v_bstride; int32_t ldv;
+  const float* p; int32_t ldp; int32_t P; int32_t center; /* [P, ldp] */
+  const float* bias_u; const float* bias_v;              /* [heads * dh] */
+  const int32_t* lens; int32_t B; int32_t T; int32_t heads; int32_t dh; float scale;
+  float* out; int64_t out_bstride; int32_t ldo;          /* [B, T, ldo] */
+} mi355_relpos_attention_args;
+int mi355_relpos_attention(const mi355_relpos_attention_args* a, void* stream);
+
+#define MI355_GLU_DWCONV_MAX_TAPS 31
+/* Convolution.__call__ between its two pointwise convs (conformer.py:83-87), channels-last.  x [B, L, 2 C] is pointwise conv 1's
+ * output; with g[t, c] = x[t, c] * sigmoid(x[t, C + c]) for 0 <= t < lens[b] and 0 elsewhere:
+ *   z = b[c] + sum_{k<K} w[c, k] * g[t + k - (K - 1) / 2, c],   y[t, c] = z * sigmoid(z)   (full-precision expf),
+ * rows lens[b] <= t < L are written as zeros.  w / b carry the depthwise bias and the BatchNorm running statistics, folded by the
+ * caller.  K odd, <= MI355_GLU_DWCONV_MAX_TAPS; C a multiple of 4; y must not alias x. */
+typedef struct {
+  const float* x; int64_t x_bstride; int32_t ldx;        /* [B, L, ldx], ldx >= 2 C */
+  const float* w; const float* b;                        /* [C, K]; [C] nullable => 0 */
+  int32_t K; int32_t C; int32_t L; const int32_t* lens; int32_t B;   /* lens [B] nullable => L */
+  float* y; int64_t y_bstride; int32_t ldy;              /* [B, L, ldy] */
+} mi355_glu_dwconv_silu_args;
+int mi355_glu_dwconv_silu(const mi355_glu_dwconv_silu_args* a, void* stream);
+
+/* The 3 x 3 / stride 2 / pad 1 convs of DwStridingSubsampling (conformer.py:174-207), channels-last, To = (T - 1) / 2 + 1,
+ * Fo = (F - 1) / 2 + 1:
+ *   y[b, t, f, c] = act( bias[c] + sum_{kh,kw} w[c, kh, kw] * x[b, 2t + kh - 1, 2f + kw - 1, c * in_cstride] ),
+ * in_cstride 0: x is [B, T, F] (the first conv's single input channel), 1: x is [B, T, F, C] (depthwise).  Input rows at or beyond
+ * lens_in[b] and everything outside [0, T) x [0, F) read as zero; output rows at or beyond lens_out[b] are written as zeros. */
+typedef struct {
+  const float* x; int64_t x_bstride;                     /* [B, T, F (, C)] */
+  const float* w; const float* bias;                     /* [C, 3, 3]; [C] nullable => 0 */
+  int32_t B; int32_t T; int32_t F; int32_t C; int32_t in_cstride; int32_t relu;
+  const int32_t* lens_in; const int32_t* lens_out;       /* [B] nullable => T / To */
+  float* y; int64_t y_bstride;                           /* [B, To, Fo, C] */
+} mi355_stencil2d_k3s2_args;
+int mi355_stencil2d_k3s2(const mi355_stencil2d_k3s2_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bidirectional LSTM recurrence (the x-projection is a conv_gemm).
  * Replaces the per-time-step Python loops of LSTM._forward_direction/_backward_direction
  * (modules.py:150-240): gates i,f,g,o; c = f*c + i*g; h = o*tanh(c).

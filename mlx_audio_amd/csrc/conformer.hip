@@ -1,0 +1,351 @@
+// FastConformer encoder (gfx950): the three pieces the library could not express.
+// Reference call sites: RelPositionMultiHeadAttention.__call__ (stt/models/parakeet/attention.py:93-137: (q + u) k^T and the rel_shift of
+// (q + v) p^T under one softmax), Convolution.__call__ (conformer.py:79-90: GLU -> depthwise conv -> BatchNorm on running statistics -> SiLU) and
+// the 3 x 3 / stride 2 convs of DwStridingSubsampling (conformer.py:174-207).  All three are plain float32 with a fixed summation order: no atomics,
+// and nothing in the order depends on the launch geometry, so two calls on the same bytes give the same bits.
+#include "common.h"
+
+namespace {
+
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+constexpr float kLog2e = 1.4426950408889634f;
+
+// ---------------------------------------------------------------------------------------------------- relative-position attention
+// flash_attn_kernel's tiling (flash_attn.hip): one workgroup = 128 queries x one head, 4 waves x 32 queries, 32-key stages of K / V through LDS,
+// both contractions on v_mfma_f32_32x32x2_f32 in the transposed orientation (a lane owns ONE query column), online softmax in the log2 domain.
+//
+// The position term.  rel_shift is out[i, j] = bd[i, T - 1 - i + j]: score (i, j) takes the table row of distance i - j, row center - (i - j).
+// For a wave's 32 queries i0 .. i0 + 31 and the stage's 32 keys j0 .. j0 + 31 those are the 63 consecutive rows R0 .. R0 + 62,
+// R0 = center - (i0 - j0) - 31, and pair (i0 + c, j0 + jj) sits at band row jj + 31 - c.  The four waves' bands overlap: the workgroup stages
+// the 159 rows from the last wave's R0 once per stage (rows outside the table are clamped: only masked pairs read them).  Each wave computes
+// BD^T = P_band (Q + v)^T as two 32-row MFMA blocks, writes it to its own LDS slab as [band row][query] and reads its entry back at row
+// jj + 31 - c: the skew is a per-lane row offset (consecutive lanes hit consecutive banks: (jj + 31 - c) * 32 + c = const - 31 c).
+// No [T, T] or [T, 2T - 1] matrix exists outside LDS; there is no workspace.
+constexpr int kRelKB = 32;                       // keys per stage
+constexpr int kRelBand = kRelKB + 127;           // table rows the four waves of a stage need
+template <int DH>
+constexpr int relpos_lds_floats() { return (2 * kRelKB + kRelBand) * (DH + 1) + 4 * 64 * 32; }
+
+template <int DH>
+__global__ __launch_bounds__(256) void relpos_attn_kernel(const mi355_relpos_attention_args a) {
+  constexpr int KB = kRelKB;
+  constexpr int LD = DH + 1;   // padded LDS row, floats: the A-operand ds_read_b32 of every phase is bank-conflict free
+  constexpr int NDB = DH / 32;
+  constexpr int NLD = (KB * DH / 4) / 256;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* Ks = smem;
+  float* Vs = Ks + KB * LD;
+  float* Ps = Vs + KB * LD;
+  float* Bs = Ps + kRelBand * LD;   // [wave][64 band rows][32 queries]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
+  const int h = blockIdx.y, b = blockIdx.z;
+  const int len = a.lens ? min(max(a.lens[b], 0), a.T) : a.T;
+  const int q0 = blockIdx.x * 128;
+  float* obase = a.out + (int64_t)b * a.out_bstride + h * DH;
+  if (q0 >= len) {   // a block of padding rows: zeros
+    for (int e = tid; e < 128 * (DH / 4); e += 256) {
+      const int r = q0 + e / (DH / 4);
+      if (r < a.T) *(float4*)(obase + (int64_t)r * a.ldo + (e % (DH / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
+  const int i0 = q0 + wave * 32;
+  const int qi = i0 + c;
+  const bool wave_active = i0 < len;
+  const int qic = qi < len ? qi : len - 1;
+
+  // (q + u) and (q + v), pre-scaled into the log2 domain: the B operands of K Q^T and P_band Q^T; step s needs element 2s + half
+  float qu[DH / 2], qv[DH / 2];
+  {
+    const float* qrow = a.q + (int64_t)b * a.q_bstride + (int64_t)qic * a.ldq + h * DH;
+    const float* ur = a.bias_u + h * DH;
+    const float* vr = a.bias_v + h * DH;
+    const float sc = a.scale * kLog2e;
+#pragma unroll
+    for (int s = 0; s < DH / 2; ++s) {
+      const float2 t = *(const float2*)(qrow + 2 * s);
+      const float qe = half ? t.y : t.x;
+      qu[s] = (qe + ur[2 * s + half]) * sc;
+      qv[s] = (qe + vr[2 * s + half]) * sc;
+    }
+  }
+
+  const float* kbase = a.k + (int64_t)b * a.k_bstride + h * DH;
+  const float* vbase = a.v + (int64_t)b * a.v_bstride + h * DH;
+  const float* pbase = a.p + h * DH;
+
+  float4 kpre[NLD], vpre[NLD];
+  auto prefetch = [&](int kb) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int e = i * 256 + tid;
+      const int row = e / (DH / 4), c4 = e % (DH / 4);
+      int j = kb + row;
+      j = j < len ? j : len - 1;   // clamp: finite data, masked below
+      kpre[i] = *(const float4*)(kbase + (int64_t)j * a.ldk + c4 * 4);
+      vpre[i] = *(const float4*)(vbase + (int64_t)j * a.ldv + c4 * 4);
+    }
+  };
+  auto commit = [&](int kb) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int e = i * 256 + tid;
+      const int row = e / (DH / 4), c4 = e % (DH / 4);
+      float* kd = Ks + row * LD + c4 * 4;
+      float* vd = Vs + row * LD + c4 * 4;
+      kd[0] = kpre[i].x; kd[1] = kpre[i].y; kd[2] = kpre[i].z; kd[3] = kpre[i].w;
+      vd[0] = vpre[i].x; vd[1] = vpre[i].y; vd[2] = vpre[i].z; vd[3] = vpre[i].w;
+    }
+    // the stage's band of the position table: LDS row x holds table row rlo + x (the last wave's R0 first)
+    const int rlo = a.center - (q0 + 96) + kb - 31;
+    for (int e = tid; e < kRelBand * (DH / 4); e += 256) {
+      const int x = e / (DH / 4), c4 = e % (DH / 4);
+      const int r = min(max(rlo + x, 0), a.P - 1);
+      const float4 t = *(const float4*)(pbase + (int64_t)r * a.ldp + c4 * 4);
+      float* pd = Ps + x * LD + c4 * 4;
+      pd[0] = t.x; pd[1] = t.y; pd[2] = t.z; pd[3] = t.w;
+    }
+  };
+
+  f32x16 o[NDB];
+#pragma unroll
+  for (int d = 0; d < NDB; ++d)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  float m = -INFINITY, lsum = 0.f;
+  float* bw = Bs + wave * (64 * 32);
+
+  prefetch(0);
+  for (int kb = 0; kb < len; kb += KB) {
+    __syncthreads();   // everyone is done reading the previous stage (K, V, the band and the wave's own slab)
+    commit(kb);
+    __syncthreads();
+    if (kb + KB < len) prefetch(kb + KB);
+    if (!wave_active) continue;
+    // ---- BD^T: band rows x0 .. x0 + 63 of the stage (this wave's R0 is 32 (3 - wave) rows behind the stage's first row)
+    const int x0 = 96 - 32 * wave;
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+      f32x16 bd;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bd[r] = 0.f;
+      const float* prow = Ps + min(x0 + blk * 32 + c, kRelBand - 1) * LD + half;   // band row 63 (x = 159 for wave 0) is never read back
+#pragma unroll
+      for (int s = 0; s < DH / 2; ++s) bd = __builtin_amdgcn_mfma_f32_32x32x2f32(prow[2 * s], qv[s], bd, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bw[(blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 32 + c] = bd[r];
+    }
+    // ---- S^T block (32 keys x 32 queries)
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const float* krow = Ks + c * LD + half;
+#pragma unroll
+    for (int s = 0; s < DH / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[2 * s], qu[s], acc, 0, 0, 0);
+    wave_lds_sync();   // the slab is this wave's own
+    // ---- + the skewed position term, mask (only a stage that touches len), online softmax (per-lane query)
+    const bool edge = kb + KB > len;
+    float bm = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int jj = (r & 3) + 8 * (r >> 2) + 4 * half;
+      acc[r] += bw[(jj + 31 - c) * 32 + c];
+      if (edge && kb + jj >= len) acc[r] = -INFINITY;
+      bm = fmaxf(bm, acc[r]);
+    }
+    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    const float m_new = fmaxf(m, bm);   // finite: key kb is valid in every stage
+    const float alpha = exp2f(m - m_new);   // m = -inf -> 0
+    float ps = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[r] = exp2f(acc[r] - m_new);   // -inf -> 0
+      ps += acc[r];
+    }
+    lsum = lsum * alpha + ps;
+    m = m_new;
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+    // ---- O^T += V^T P^T : step s contracts keys (s&3) + 8*(s>>2) + 4*half, which is where acc[s] lives
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float* vrow = Vs + ((s & 3) + 8 * (s >> 2) + 4 * half) * LD + c;
+#pragma unroll
+      for (int d = 0; d < NDB; ++d) o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[d * 32], acc[s], o[d], 0, 0, 0);
+    }
+  }
+
+  if (qi >= a.T) return;
+  float* orow = obase + (int64_t)qi * a.ldo;
+  if (qi >= len) {   // padding rows inside a block that has valid ones
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+#pragma unroll
+      for (int c4 = 0; c4 < 4; ++c4) *(float4*)(orow + d * 32 + 8 * c4 + 4 * half) = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  lsum += __shfl_xor(lsum, 32, 64);
+  const float inv = 1.0f / lsum;
+#pragma unroll
+  for (int d = 0; d < NDB; ++d)
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4)
+      *(float4*)(orow + d * 32 + 8 * c4 + 4 * half) = make_float4(o[d][c4 * 4] * inv, o[d][c4 * 4 + 1] * inv, o[d][c4 * 4 + 2] * inv, o[d][c4 * 4 + 3] * inv);
+}
+
+// ---------------------------------------------------------------------------------------------------- GLU -> depthwise conv -> (BatchNorm) -> SiLU
+__device__ __forceinline__ float sigmoid_f32(const float x) { return 1.0f / (1.0f + expf(-x)); }
+
+constexpr int kGluRun = 32;   // consecutive time steps per thread (fsmn_memory_kernel's shape: s3.hip)
+
+// One thread = one channel x kGluRun time steps; the 64 lanes of a wave are 64 adjacent channels (every row access is one 256-byte request for each
+// half of x), the four waves of a workgroup four consecutive runs.  The gated window and the channel's taps live in registers.  KMAX is the
+// register window's tap count: shorter kernels are centred in it (0 * finite adds nothing to the sum).
+template <int KMAX>
+__global__ __launch_bounds__(256) void glu_dwconv_silu_kernel(const mi355_glu_dwconv_silu_args a) {
+  constexpr int kHalf = (KMAX - 1) / 2, kWin = kGluRun + KMAX - 1;
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int t0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * kGluRun;
+  const int b = blockIdx.z;
+  if (c >= a.C || t0 >= a.L) return;
+  const int len = a.lens ? min(max(a.lens[b], 0), a.L) : a.L;
+  const float* xb = a.x + (int64_t)b * a.x_bstride + c;
+  float w[KMAX];
+  const int shift = kHalf - (a.K - 1) / 2;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) {
+    const int k = j - shift;
+    w[j] = (k >= 0 && k < a.K) ? a.w[(int64_t)c * a.K + k] : 0.f;
+  }
+  const float bias = a.b ? a.b[c] : 0.f;
+  float win[kWin];
+#pragma unroll
+  for (int i = 0; i < kWin; ++i) {
+    const int r = t0 - kHalf + i;
+    float g = 0.f;
+    if (r >= 0 && r < len) {   // rows at or beyond lens[b] (<= L) and outside [0, L) are zero: never dereferenced
+      const float* xr = xb + (int64_t)r * a.ldx;
+      g = xr[0] * sigmoid_f32(xr[a.C]);
+    }
+    win[i] = g;
+  }
+  float* yb = a.y + (int64_t)b * a.y_bstride + c;
+#pragma unroll
+  for (int i = 0; i < kGluRun; ++i) {
+    const int t = t0 + i;
+    if (t >= a.L) break;
+    float z = bias;
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) z = fmaf(w[j], win[i + j], z);   // taps in order k = 0 .. K - 1
+    yb[(int64_t)t * a.ldy] = t < len ? z * sigmoid_f32(z) : 0.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- 3 x 3 / stride 2 / pad 1 stencil, channels-last
+// One thread = one output (b, t, f, c), c fastest: the 64 lanes of a wave read 64 adjacent channels of each tap (in_cstride = 1) or one
+// broadcast value (in_cstride = 0, the single-channel first conv).  bias, then the nine taps in (kh, kw) order.
+__global__ __launch_bounds__(256) void stencil2d_k3s2_kernel(const mi355_stencil2d_k3s2_args a, const int To, const int Fo, const int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % a.C);
+  int64_t r = idx / a.C;
+  const int f = (int)(r % Fo);
+  r /= Fo;
+  const int t = (int)(r % To), b = (int)(r / To);
+  const int len_in = a.lens_in ? min(max(a.lens_in[b], 0), a.T) : a.T;
+  const int len_out = a.lens_out ? min(max(a.lens_out[b], 0), To) : To;
+  float* yp = a.y + (int64_t)b * a.y_bstride + ((int64_t)t * Fo + f) * a.C + c;
+  if (t >= len_out) {
+    *yp = 0.f;
+    return;
+  }
+  const int cin = a.in_cstride ? a.C : 1;
+  const float* xb = a.x + (int64_t)b * a.x_bstride + (int64_t)c * a.in_cstride;
+  const float* wc = a.w + (int64_t)c * 9;
+  float s = a.bias ? a.bias[c] : 0.f;
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh) {
+    const int ti = 2 * t + kh - 1;
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const int fi = 2 * f + kw - 1;
+      const bool ok = ti >= 0 && ti < len_in && fi >= 0 && fi < a.F;
+      const float xv = ok ? xb[((int64_t)ti * a.F + fi) * cin] : 0.f;
+      s = fmaf(wc[kh * 3 + kw], xv, s);
+    }
+  }
+  *yp = a.relu ? fmaxf(s, 0.f) : s;
+}
+
+template <int DH>
+int launch_relpos(const mi355_relpos_attention_args& a, hipStream_t st) {
+  static bool configured = false;   // one attribute call per instantiation
+  constexpr int lds = relpos_lds_floats<DH>() * (int)sizeof(float);
+  if (!configured) {
+    hipError_t e = hipFuncSetAttribute((const void*)relpos_attn_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    MI355_REQUIRE(e == hipSuccess, "relpos_attention: cannot reserve %d bytes of LDS: %s", lds, hipGetErrorString(e));
+    configured = true;
+  }
+  MI355_CLEAR_ERROR();
+  hipLaunchKernelGGL(relpos_attn_kernel<DH>, dim3((unsigned)((a.T + 127) / 128), (unsigned)a.heads, (unsigned)a.B), dim3(256), lds, st, a);
+  MI355_LAUNCH_CHECK("relpos_attention");
+  return MI355_OK;
+}
+
+}  // namespace
+
+extern "C" int mi355_relpos_attention(const mi355_relpos_attention_args* ap, void* stream) {
+  MI355_REQUIRE(ap && ap->q && ap->k && ap->v && ap->p && ap->bias_u && ap->bias_v && ap->out, "relpos_attention: null tensor");
+  const mi355_relpos_attention_args a = *ap;
+  MI355_REQUIRE(a.B > 0 && a.B <= 65535 && a.heads > 0 && a.heads <= 65535 && a.T >= 1, "relpos_attention: bad shape");
+  MI355_REQUIRE(a.dh == 64 || a.dh == 128, "relpos_attention: dh must be 64 or 128 (got %d)", a.dh);
+  const int hd = a.heads * a.dh;
+  MI355_REQUIRE(a.ldq >= hd && a.ldk >= hd && a.ldv >= hd && a.ldo >= hd && a.ldp >= hd, "relpos_attention: a row stride is smaller than heads * dh");
+  MI355_REQUIRE(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && a.ldo % 4 == 0 && a.ldp % 4 == 0 && a.q_bstride % 4 == 0 && a.k_bstride % 4 == 0 &&
+                    a.v_bstride % 4 == 0 && a.out_bstride % 4 == 0 && ((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.p | (uintptr_t)a.out) % 16 == 0,
+                "relpos_attention: rows must be 16-byte aligned");
+  MI355_REQUIRE(a.P >= 1 && (int64_t)a.center - (a.T - 1) >= 0 && (int64_t)a.center + a.T - 1 < a.P,
+                "relpos_attention: the position table (P = %d rows, center %d) does not hold the distances -(T - 1) .. T - 1 of T = %d", a.P, a.center, a.T);
+  return a.dh == 64 ? launch_relpos<64>(a, (hipStream_t)stream) : launch_relpos<128>(a, (hipStream_t)stream);
+}
+
+extern "C" int mi355_glu_dwconv_silu(const mi355_glu_dwconv_silu_args* ap, void* stream) {
+  MI355_REQUIRE(ap && ap->x && ap->w && ap->y, "glu_dwconv_silu: null tensor");
+  const mi355_glu_dwconv_silu_args a = *ap;
+  MI355_REQUIRE(a.B > 0 && a.B <= 65535 && a.C > 0 && a.C % 4 == 0 && a.L > 0, "glu_dwconv_silu: bad shape (C must be a multiple of 4)");
+  MI355_REQUIRE(a.K >= 1 && a.K <= MI355_GLU_DWCONV_MAX_TAPS && (a.K & 1) == 1, "glu_dwconv_silu: K must be odd and <= %d (got %d)", MI355_GLU_DWCONV_MAX_TAPS, a.K);
+  MI355_REQUIRE(a.ldx >= 2 * a.C && a.ldy >= a.C, "glu_dwconv_silu: a row stride is too small (x rows hold 2 C values)");
+  MI355_REQUIRE((const void*)a.y != (const void*)a.x, "glu_dwconv_silu: y must not alias x (a step reads its neighbours' values)");
+  const int64_t gy = ((int64_t)a.L + 4 * kGluRun - 1) / (4 * kGluRun);
+  MI355_REQUIRE(gy <= 65535, "glu_dwconv_silu: sequence too long");
+  const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)gy, (unsigned)a.B);
+  MI355_CLEAR_ERROR();
+  if (a.K <= 9) hipLaunchKernelGGL(glu_dwconv_silu_kernel<9>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(glu_dwconv_silu_kernel<MI355_GLU_DWCONV_MAX_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  MI355_LAUNCH_CHECK("glu_dwconv_silu");
+  return MI355_OK;
+}
+
+extern "C" int mi355_stencil2d_k3s2(const mi355_stencil2d_k3s2_args* ap, void* stream) {
+  MI355_REQUIRE(ap && ap->x && ap->w && ap->y, "stencil2d_k3s2: null tensor");
+  const mi355_stencil2d_k3s2_args a = *ap;
+  MI355_REQUIRE(a.B > 0 && a.T > 0 && a.F > 0 && a.C > 0, "stencil2d_k3s2: bad shape");
+  MI355_REQUIRE(a.in_cstride == 0 || a.in_cstride == 1, "stencil2d_k3s2: in_cstride is 0 (one input channel) or 1 (depthwise), got %d", a.in_cstride);
+  const int To = (a.T - 1) / 2 + 1, Fo = (a.F - 1) / 2 + 1;
+  const int64_t total = (int64_t)a.B * To * Fo * a.C;
+  const int64_t blocks = (total + 255) / 256;
+  MI355_REQUIRE(blocks <= 0x7fffffff, "stencil2d_k3s2: too many outputs");
+  MI355_REQUIRE((int64_t)a.T * a.F * (a.in_cstride ? a.C : 1) <= a.x_bstride && (int64_t)To * Fo * a.C <= a.y_bstride, "stencil2d_k3s2: a batch stride is smaller than an item");
+  MI355_CLEAR_ERROR();
+  hipLaunchKernelGGL(stencil2d_k3s2_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, To, Fo, total);
+  MI355_LAUNCH_CHECK("stencil2d_k3s2");
+  return MI355_OK;
+}

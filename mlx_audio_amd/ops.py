@@ -1103,6 +1103,72 @@ def fsq_encode(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], *, l
     return (codes, h) if return_h else codes
 
 
+GLU_DWCONV_MAX_TAPS = 31  # MI355_GLU_DWCONV_MAX_TAPS
+
+
+def _lens_arg(lens: Optional[torch.Tensor], B: int):
+    if lens is not None:
+        assert lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous() and lens.is_cuda
+    return _ptr(lens)
+
+
+def relpos_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch.Tensor, bias_u: torch.Tensor, bias_v: torch.Tensor, out: torch.Tensor, *,
+                     heads: int, dh: int, center: int, scale: Optional[float] = None, lens: Optional[torch.Tensor] = None):
+    """``out_i = sum_j softmax_j(scale ((q_i + u) . k_j + (q_i + v) . p[center - (i - j)])) v_j`` over ``j < lens[b]`` (``mi355_relpos_attention``):
+    the Conformer's relative-position attention behind its projections.  ``q`` / ``k`` / ``v`` / ``out`` channels-last views [B, T, heads * dh]
+    (thirds of a fused buffer or contiguous), ``p`` the projected position table [P, heads * dh] whose row ``center`` is distance 0, ``bias_u`` /
+    ``bias_v`` [heads * dh].  Rows at and beyond ``lens[b]`` come back zero.  The table must hold the distances -(T - 1) .. T - 1."""
+    B, T, C, qbs, ldq = _nlc(q)
+    Bk, Tk, Ck, kbs, ldk = _nlc(k)
+    Bv, Tv, Cv, vbs, ldv = _nlc(v)
+    Bo, To, Co, obs, ldo = _nlc(out)
+    hd = heads * dh
+    assert (Bk, Tk) == (B, T) and (Bv, Tv) == (B, T) and (Bo, To) == (B, T) and min(C, Ck, Cv, Co) >= hd
+    assert p.dim() == 2 and p.stride(1) == 1 and p.shape[1] >= hd and p.dtype == torch.float32 and p.is_cuda
+    for t in (bias_u, bias_v):
+        assert t.dtype == torch.float32 and t.numel() == hd and t.is_contiguous() and t.is_cuda
+    _lib.call_struct("mi355_relpos_attention", "mi355_relpos_attention_args", _stream(), q=_ptr(q), q_bstride=qbs, ldq=ldq, k=_ptr(k), k_bstride=kbs,
+                     ldk=ldk, v=_ptr(v), v_bstride=vbs, ldv=ldv, p=_ptr(p), ldp=p.stride(0), P=p.shape[0], center=center, bias_u=_ptr(bias_u),
+                     bias_v=_ptr(bias_v), lens=_lens_arg(lens, B), B=B, T=T, heads=heads, dh=dh, scale=dh ** -0.5 if scale is None else scale,
+                     out=_ptr(out), out_bstride=obs, ldo=ldo)
+    return out
+
+
+def glu_dwconv_silu(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, *, lens: Optional[torch.Tensor] = None):
+    """``silu(b + sum_k w[:, k] * g[t + k - (K - 1) / 2])`` with ``g = x[..., :C] * sigmoid(x[..., C:])`` (``mi355_glu_dwconv_silu``): the middle of the
+    Conformer's convolution module, ``x`` [B, L, 2 C] -> ``y`` [B, L, C]; ``w`` [C, K] (K odd, <= ``GLU_DWCONV_MAX_TAPS``) and ``b`` [C] carry the
+    depthwise bias and the folded BatchNorm.  ``g`` is zero outside ``[0, lens[b])`` and the rows of ``y`` at and beyond ``lens[b]`` are zero."""
+    B, L, C2, xbs, ldx = _nlc(x)
+    By, Ly, C, ybs, ldy = _nlc(y)
+    assert (By, Ly) == (B, L) and C2 == 2 * C
+    assert w.dim() == 2 and w.shape[0] == C and w.is_contiguous() and w.dtype == torch.float32 and (b is None or (b.numel() == C and b.is_contiguous() and b.dtype == torch.float32))
+    _lib.call_struct("mi355_glu_dwconv_silu", "mi355_glu_dwconv_silu_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, w=_ptr(w), b=_ptr(b),
+                     K=w.shape[1], C=C, L=L, lens=_lens_arg(lens, B), B=B, y=_ptr(y), y_bstride=ybs, ldy=ldy)
+    return y
+
+
+def stencil2d_out(n: int) -> int:
+    """k = 3, stride 2, pad 1."""
+    return (n - 1) // 2 + 1
+
+
+def stencil2d_k3s2(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], y: torch.Tensor, *, relu: bool = False,
+                   lens_in: Optional[torch.Tensor] = None, lens_out: Optional[torch.Tensor] = None):
+    """3 x 3 / stride 2 / pad 1 over (time, frequency), channels-last (``mi355_stencil2d_k3s2``): ``x`` [B, T, F] (one input channel feeding every
+    output channel) or [B, T, F, C] (depthwise), ``w`` [C, 3, 3], ``y`` [B, To, Fo, C].  Input rows at and beyond ``lens_in[b]`` read as zero, output
+    rows at and beyond ``lens_out[b]`` are written as zero."""
+    assert x.dtype == torch.float32 and x.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and x.dim() in (3, 4)
+    B, T, F = x.shape[:3]
+    C = y.shape[3]
+    assert x[0].is_contiguous() and y[0].is_contiguous() and (x.dim() == 3 or x.shape[3] == C)
+    assert tuple(y.shape) == (B, stencil2d_out(T), stencil2d_out(F), C), (tuple(y.shape), tuple(x.shape))
+    assert tuple(w.shape) == (C, 3, 3) and w.is_contiguous() and w.dtype == torch.float32 and (bias is None or (bias.numel() == C and bias.is_contiguous()))
+    _lib.call_struct("mi355_stencil2d_k3s2", "mi355_stencil2d_k3s2_args", _stream(), x=_ptr(x), x_bstride=x.stride(0) if B > 1 else x[0].numel(), w=_ptr(w),
+                     bias=_ptr(bias), B=B, T=T, F=F, C=C, in_cstride=int(x.dim() == 4), relu=int(relu), lens_in=_lens_arg(lens_in, B),
+                     lens_out=_lens_arg(lens_out, B), y=_ptr(y), y_bstride=y.stride(0) if B > 1 else y[0].numel())
+    return y
+
+
 def sample(logits: torch.Tensor, out: torch.Tensor, *, V: Optional[int] = None, suppress_mask=None, history=None, n_hist: int = 0,
            hist_len=None, repetition_penalty: float = 1.0, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
            gumbel=None, done=None, done_token: int = 0, filtered=None):

@@ -1,5 +1,5 @@
 """Parakeet's audio front end (stt/models/parakeet/audio.py): the same ``PreprocessArgs`` and ``log_mel_spectrogram(x, args)`` on the MI355X --
-pre-emphasis + one fused STFT -> |X|^2 -> mel -> ln(. + guard) kernel + the normalisation.  The Parakeet model itself is outside SURVEY 8(a)."""
+pre-emphasis + one fused STFT -> |X|^2 -> mel -> ln(. + guard) kernel + the normalisation.  Its consumer is ``parakeet.py`` (``ParakeetCTC``: the FastConformer encoder and the CTC head on the device)."""
 from dataclasses import dataclass
 
 import torch

@@ -1,5 +1,6 @@
 """Sortformer's feature extraction (vad/models/sortformer/sortformer.py:36-123) on the MI355X: NeMo FilterbankFeatures for a BATCH of waveforms in one
-fused kernel launch.  The diarisation model itself is outside SURVEY 8(a)."""
+fused kernel launch.  The diarisation model itself is outside SURVEY 8(a); the FastConformer encoder inside it is built
+(``stt/models/parakeet/conformer.py``)."""
 from typing import Optional
 
 import torch
