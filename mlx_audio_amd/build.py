@@ -40,7 +40,7 @@ def _hipcc() -> str:
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    for name in SOURCES + ["common.h", "conv_common.h", "conv_ws4.h", "fft_fast.h", "fft_tw.h"]:
+    for name in SOURCES + sorted(n for n in os.listdir(CSRC) if n.endswith(".h")):   # every header: a new one must trigger a rebuild too
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(f.read())
     with open(HEADER, "rb") as f:

@@ -9,13 +9,6 @@ namespace {
 
 constexpr int kMaxT = 512;
 
-// LDS hand-over between lanes of ONE wavefront (waves of a block may exit early, so no s_barrier)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(256) void attention_kernel(const mi355_attention_args a) {
   __shared__ float qs[4][64];
   __shared__ float ps[4][kMaxT];
@@ -27,7 +20,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const mi355_attention_ar
   const float* base = a.qkv + (int64_t)b * a.bstride;
   const float* qrow = base + (int64_t)q * a.ld + h * a.dh;
   if (lane < a.dh) qs[w][lane] = qrow[lane];
-  wave_lds_sync();
+  wave_lds_fence();   // LDS hand-over between lanes of ONE wavefront (waves of a block may exit early, so no s_barrier)
   const float inv = sqrtf((float)a.dh);
   float sc[kMaxT / 64];
   float mx = -INFINITY;
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const mi355_attention_ar
     const int j = i * 64 + lane;
     if (j < len) ps[w][j] = ps[w][j] / sum;  // softmax, then probs @ V like the reference
   }
-  wave_lds_sync();
+  wave_lds_fence();
   if (lane < a.dh) {
     const float* vcol = base + 2 * D + h * a.dh + lane;
     float o = 0.f;

@@ -196,6 +196,14 @@ struct FakeQuant {
   }
 };
 
+// Wave-level LDS fence: the LDS traffic this wave issued before it is visible to every lane of the wave afterwards (the LDS queue of a wave is in
+// order).  For LDS that only ONE wave touches: no s_barrier, the other waves of the workgroup are not involved.
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

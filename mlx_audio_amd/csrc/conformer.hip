@@ -7,12 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr float kLog2e = 1.4426950408889634f;
 
 // ---------------------------------------------------------------------------------------------------- relative-position attention
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(256) void relpos_attn_kernel(const mi355_relpos_att
     const float* krow = Ks + c * LD + half;
 #pragma unroll
     for (int s = 0; s < DH / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[2 * s], qu[s], acc, 0, 0, 0);
-    wave_lds_sync();   // the slab is this wave's own
+    wave_lds_fence();   // the slab is this wave's own
     // ---- + the skewed position term, mask (only a stage that touches len), online softmax (per-lane query)
     const bool edge = kb + KB > len;
     float bm = -INFINITY;

@@ -14,6 +14,7 @@
 //     as the dense dot product in that order) -> log -> staged in LDS -> one contiguous store of the tile's [frames, n_mels] block.
 //     The spectrum never exists in HBM; HBM traffic = the samples once (overlapping frames hit in L2) + the log-mel block.
 #pragma once
+#include "common.h"
 #include "fft_tw.h"
 
 namespace mi355fft {
@@ -124,12 +125,6 @@ struct FastArgs {
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
   if (v >= 0.f) atomicMax((int*)addr, __float_as_int(v));
   else atomicMin((unsigned int*)addr, __float_as_uint(v));
-}
-// order this wave's LDS traffic: everything issued before is visible to every lane of the wave afterwards (no s_barrier)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // MODE 0: complex spectrum out [B, n_frames, NB, 2];  MODE 1: log-mel out [B, n_frames, n_mels]
@@ -307,10 +302,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(WAVES * 64, WAVES * 64), a
         float* dst = c.out + ((int64_t)b * c.n_frames + f0) * c.n_mels;
         for (int i = lane; i < nf * c.n_mels; i += 64) dst[i] = y0;
       }
-      wave_sync();   // the buffer is rewritten by the next tile's loads
+      wave_lds_fence();   // the buffer is rewritten by the next tile's loads
       continue;
     }
-    wave_sync();
+    wave_lds_fence();
     // ---- pass 1: lane (pair, n2): N1-point DFT down column n2, inter-pass twiddle W_N^{n2 k1}, back into the same column
     if (lane < PW * N2) {
       const int pr = lane / N2, n2 = lane - pr * N2;
@@ -326,7 +321,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(WAVES * 64, WAVES * 64), a
         col[k1 * PR] = make_float2(v[k1].x * w.x - v[k1].y * w.y, v[k1].x * w.y + v[k1].y * w.x);
       }
     }
-    wave_sync();
+    wave_lds_fence();
     // ---- pass 2: lane (pair, k1): N2-point DFT along row k1; X[k1 + N1 k2] goes back in natural order (all reads before any write)
     {
       float2 u[N2];
@@ -338,14 +333,14 @@ __global__ __attribute__((amdgpu_flat_work_group_size(WAVES * 64, WAVES * 64), a
         for (int n2 = 0; n2 < N2; ++n2) u[n2] = row[n2];
         dft<N2>(u);
       }
-      wave_sync();
+      wave_lds_fence();
       if (act) {
         float2* dst = z + pr * PITCH + k1;
 #pragma unroll
         for (int k2 = 0; k2 < N2; ++k2) dst[N1 * k2] = u[k2];
       }
     }
-    wave_sync();
+    wave_lds_fence();
     // ---- the two real transforms: Xa = (Z[k] + conj Z[N-k]) / 2, Xb = (Z[k] - conj Z[N-k]) / (2i).  MODE 1: the powers of a lane's bins wait in
     // registers until every lane has read its spectrum values, then go back on top of the transform buffer as the rows the mel stage reads
     constexpr int NS = (PW * NB + 63) / 64;
@@ -371,7 +366,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(WAVES * 64, WAVES * 64), a
         }
       }
     }
-    wave_sync();
+    wave_lds_fence();
     if constexpr (MODE == 1) {
 #pragma unroll
       for (int q = 0; q < NS; ++q) {
@@ -382,7 +377,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(WAVES * 64, WAVES * 64), a
           pw[(2 * pr + 1) * NBP + k] = pb_r[q];
         }
       }
-      wave_sync();
+      wave_lds_fence();
     }
     if constexpr (MODE == 1) {
       // ---- mel rows over their spans, log, staged as [frame][n_mels | 1] on top of the (now dead) transform buffer
@@ -423,14 +418,14 @@ __global__ __attribute__((amdgpu_flat_work_group_size(WAVES * 64, WAVES * 64), a
         for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
         max_v = fmaxf(max_v, lmax);
       }
-      wave_sync();
+      wave_lds_fence();
       const int nf = min(2 * PW, c.n_frames - f0);
       float* dst = c.out + ((int64_t)b * c.n_frames + f0) * n_mels;
       for (int i = lane; i < nf * n_mels; i += 64) {
         const int fl = i / n_mels, m = i - fl * n_mels;
         dst[i] = stage[fl * SP + m];
       }
-      wave_sync();
+      wave_lds_fence();
     }
   }
   if constexpr (MODE == 1) {

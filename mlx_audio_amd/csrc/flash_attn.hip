@@ -31,12 +31,6 @@
 
 namespace {
 
-__device__ __forceinline__ void wave_lds_sync2() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr float kLog2e = 1.4426950408889634f;
 
 // K / V element types: KVT 0 = float32, 1 = bfloat16, 2 = float16 (mi355_flash_attn_args.kv_dtype = MI355_KV_F32 / MI355_KV_BF16 / MI355_KV_F16).  A 16-bit cache
@@ -246,6 +240,7 @@ __device__ __forceinline__ f32x16 mfma32_16(const uint4 a, const uint4 b, const 
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
+// not linear_common.h's split_hi_lo: the fp16 branch packs round-TOWARD-ZERO (one instruction per pair), split_hi_lo rounds to nearest
 template <bool F16>
 __device__ __forceinline__ void split_pair(const float x, const float y, uint32_t& hi, uint32_t& lo) {
   if constexpr (F16) {
@@ -579,7 +574,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const mi355_flash_
         rope_pair(x0, x1, c, sn, y0, y1);
         x0 = y0; x1 = y1;
       }
-      wave_lds_sync2();
+      wave_lds_fence();
       if (act) {
         if (is_q) { vec[i0] = x0 * qsc; vec[i1] = x1 * qsc; }
         else { vec[i0] = kv_round<KVT>(x0); vec[i1] = kv_round<KVT>(x1); }
@@ -673,16 +668,16 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const mi355_flash_
         }
       }
     }
-    wave_lds_sync2();
+    wave_lds_fence();
     const float s = ps[wave][lane];
-    wave_lds_sync2();  // every lane has its score before ps is overwritten with the probabilities
+    wave_lds_fence();  // every lane has its score before ps is overwritten with the probabilities
     const float m_new = fmaxf(m, wave_max_fast(s));  // finite: key kb itself is visible (DPP reductions: every lane of the wave is here)
     const float alpha = exp2f(m - m_new);
     const float p = exp2f(s - m_new);
     l = l * alpha + wave_sum_fast(p);
     m = m_new;
     ps[wave][lane] = p;
-    wave_lds_sync2();
+    wave_lds_fence();
     const int n = kend - kb < 64 ? kend - kb : 64;
 #pragma unroll
     for (int i = 0; i < ND; ++i) o[i] *= alpha;
@@ -741,13 +736,13 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const mi355_flash_
       // the probabilities in ps[wave] have been consumed: reuse the row to go from pair-per-lane back to channel-per-lane (64 channels a round)
 #pragma unroll
       for (int h2 = 0; h2 < ND; ++h2) {
-        wave_lds_sync2();
+        wave_lds_fence();
         if (r == 0 && c >= 32 * h2 && c < 32 * h2 + 32) { ps[wave][2 * (c - 32 * h2)] = o2[0]; ps[wave][2 * (c - 32 * h2) + 1] = o2[1]; }
-        wave_lds_sync2();
+        wave_lds_fence();
         o[h2] += ps[wave][lane];
       }
     }
-    wave_lds_sync2();
+    wave_lds_fence();
   }
   if (fused && wave == 0) {
     float t = 0.f;
@@ -836,7 +831,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const mi355_flash_
     if (a.out_planes) {   // the row also leaves as hi + lo planes (fragment order of mi355_rows_gemm): lane c < DH / 8 builds the piece of channels 8 c .. 8 c + 7
 #pragma unroll
       for (int i = 0; i < ND; ++i) red_o[0][i * 64 + lane] = t[i] * inv;
-      wave_lds_sync2();
+      wave_lds_fence();
       if (lane < DH / 8) {
         float e[8];
 #pragma unroll

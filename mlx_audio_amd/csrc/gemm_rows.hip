@@ -15,12 +15,12 @@
 //     separates the writes of a chunk from its fragment reads.
 //   * A workgroup owns T column tiles at a time (tile = (group * T + j) * gridDim.x + blockIdx.x): one staged chunk feeds T x (R / 16) x 4 MFMAs per
 //     k step.  Weights of the next P chunks (16 KB per wave) and the input rows of the next chunk are always in flight.
-//   * the four partial tiles meet in LDS after the last chunk; thread (n = t & 15, m = t >> 4) finishes the outputs: bias, activation, LayerScale,
-//     residual, SwiGLU pairs, split destinations (q -> buffer, k | v -> KV-cache slot, 16-bit slots included).
+//   * the four partial tiles meet in LDS after the last chunk; thread (n = t & 15, m = t >> 4) finishes the outputs (linear_finish /
+//     linear_finish_glu of linear_common.h).
 //   * fused LayerNorm / RMSNorm: a statistics pass over the rows (one read of x from L2, fp64 sums) precedes the chunk loop, any K.
 // Rows m >= M of the MFMA column space are staged as zeros and never stored.
 #include <stdlib.h>
-#include "common.h"
+#include "linear_common.h"
 
 namespace {
 
@@ -31,46 +31,6 @@ template <int MR> struct rows_cfg {
   static constexpr int T = MR == 1 ? 1 : 2;  // column tiles per workgroup pass
   static constexpr int P = 2;                // chunks of weights in flight per wave (MR = 4: 4 x 2 KB, else 8 x 2 KB; 8 waves per CU)
 };
-
-__device__ __forceinline__ float rows_act(float v, int act, float slope) {
-  switch (act) {
-    case MI355_ACT_LEAKY: return v > 0.f ? v : v * slope;
-    case MI355_ACT_GELU: return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    case MI355_ACT_SILU: return v / (1.0f + expf(-v));
-    case MI355_ACT_GELU_TANH: return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-    case MI355_ACT_ELU: return v > 0.f ? v : expm1f(v);
-    case MI355_ACT_TANH: return tanhf(v);
-    default: return v;
-  }
-}
-
-// hi + lo images of two fp32 values (low half = first value)
-template <bool F16>
-__device__ __forceinline__ void rows_split2(const float a, const float b, uint32_t& hi, uint32_t& lo) {
-  if constexpr (F16) {
-    hi = pack_f16x2(a, b);
-    const float ha = (float)__builtin_bit_cast(_Float16, (uint16_t)(hi & 0xffffu)), hb = (float)__builtin_bit_cast(_Float16, (uint16_t)(hi >> 16));
-    lo = pack_f16x2(a - ha, b - hb);
-  } else {
-    hi = pack_bf16x2(a, b);
-    const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16x2(a - ha, b - hb);
-  }
-}
-
-template <bool F16>
-__device__ __forceinline__ f32x4 rows_mfma(const uint4 a, const uint4 b, const f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // LSTM mode (mi355_lstm_seq with gate-interleaved Wh rows, lstm_seq.hip): the GEMM is one recurrence step pre = h @ Wh^T; its epilogue adds the
 // x-projection row, applies the gates (the reference's Metal kernel: codec/models/encodec/encodec.py:89-134 -- chunks i | f | g | o, sigmoid as
@@ -198,10 +158,10 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const mi355_gemv_args
           if (dbg & 2) {
             hi = __builtin_bit_cast(uint4, v0); lo = __builtin_bit_cast(uint4, v1);
           } else {
-          rows_split2<F16>(v0.x, v0.y, hi.x, lo.x);
-          rows_split2<F16>(v0.z, v0.w, hi.y, lo.y);
-          rows_split2<F16>(v1.x, v1.y, hi.z, lo.z);
-          rows_split2<F16>(v1.z, v1.w, hi.w, lo.w);
+          split_hi_lo<F16>(v0.x, v0.y, hi.x, lo.x);
+          split_hi_lo<F16>(v0.z, v0.w, hi.y, lo.y);
+          split_hi_lo<F16>(v1.x, v1.y, hi.z, lo.z);
+          split_hi_lo<F16>(v1.z, v1.w, hi.w, lo.w);
           }
           if (!(dbg & 4)) {
           win[base + m] = hi;
@@ -236,13 +196,13 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const mi355_gemv_args
               for (int r = 0; r < MR; ++r) {
                 const uint4 h0 = win[pb0 + 16 * r], h1 = win[pb1 + 16 * r], l0 = win[IMGW + pb0 + 16 * r], l1 = win[IMGW + pb1 + 16 * r];
 #pragma unroll
-                for (int j = 0; j < T; ++j) acc[j][r] = rows_mfma<F16>(w0[j], h0, acc[j][r]);
+                for (int j = 0; j < T; ++j) acc[j][r] = mfma_16x16x32<F16>(w0[j], h0, acc[j][r]);
 #pragma unroll
-                for (int j = 0; j < T; ++j) acc[j][r] = rows_mfma<F16>(w1[j], h1, acc[j][r]);
+                for (int j = 0; j < T; ++j) acc[j][r] = mfma_16x16x32<F16>(w1[j], h1, acc[j][r]);
 #pragma unroll
-                for (int j = 0; j < T; ++j) acc[j][r] = rows_mfma<F16>(w0[j], l0, acc[j][r]);
+                for (int j = 0; j < T; ++j) acc[j][r] = mfma_16x16x32<F16>(w0[j], l0, acc[j][r]);
 #pragma unroll
-                for (int j = 0; j < T; ++j) acc[j][r] = rows_mfma<F16>(w1[j], l1, acc[j][r]);
+                for (int j = 0; j < T; ++j) acc[j][r] = mfma_16x16x32<F16>(w1[j], l1, acc[j][r]);
               }
             }
           }
@@ -292,14 +252,10 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const mi355_gemv_args
         const float v0 = part(i);
         if (a.glu) {   // rows of W come in (gate, up) pairs: the even thread of a pair finishes both
           if (i & 1) continue;
-          const float g = v0 + (a.bias ? a.bias[n] : 0.f), u = part(i + 1) + (a.bias ? a.bias[n + 1] : 0.f);
-          a.y[(int64_t)m * a.ldy + (n >> 1)] = (g / (1.0f + expf(-g))) * u * a.out_scale;
+          linear_finish_glu(a, m, n, v0, part(i + 1));
           continue;
         }
-        float v = rows_act(v0 + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
-        if (a.res) v += a.res[(int64_t)m * a.ldr + n];
-        if (a.y2 && n >= a.split) store_kv_elem(a.y2, (int64_t)m * a.ldy2 + (n - a.split), v * a.out_scale, a.y2_dtype);
-        else a.y[(int64_t)m * a.ldy + n] = v * a.out_scale;
+        linear_finish(a, m, n, v0);
       }
     }
     __syncthreads();   // the next tile group restages the windows

@@ -8,9 +8,8 @@
 // bandwidth.  Here W stays in its natural row-major 16-bit layout [N, ldw] (bf16 or fp16, the checkpoint dtype); one
 // wavefront owns NC output columns, lanes stride K in 16-byte (8-element) pieces so every weight load is a fully coalesced
 // 1 KB wave access, x is staged in LDS once per workgroup in K-chunks, products accumulate in fp32 FMAs (exact on the
-// 16-bit weights) and a wave-level butterfly finishes each column.  Epilogue: bias, activation, residual, scale, and the
-// optional fused SwiGLU (interleaved gate / up rows: y[n/2] = silu(acc[n]) * acc[n+1]).  Prologue (optional): LayerNorm / RMSNorm of
-// the input rows, recomputed per workgroup; the output columns can be split over two destinations (q | k,v -> buffer | KV-cache slot).
+// 16-bit weights) and a wave-level butterfly finishes each column.  Epilogue: the shared tail of linear_common.h (here alone: a fused
+// rotary pair instead of it).  Prologue (optional): LayerNorm / RMSNorm of the input rows, recomputed per workgroup.
 // Weight element types: bf16, fp16, or fp8 (OCP e4m3fn bytes + one power-of-two scale per row, mi355_pack_rowmajor_fp8_host): a lane's 16-byte
 // piece then carries 16 elements, decoded exactly by moving the byte into binary16 position (common.h cvt_w16).
 // Dispatch: calls with 5..8 rows, 16-bit weights and K <= 2048 (K % 64 == 0) go to the matrix-pipe kernel of gemv_mfma.hip (the FMA kernel runs
@@ -21,7 +20,7 @@
 #include <map>
 #include <mutex>
 #include <utility>
-#include "common.h"
+#include "linear_common.h"
 
 namespace {
 
@@ -50,21 +49,7 @@ int resident_workgroups(const void* kern) {
   return cache[key] = per_cu * cus;
 }
 
-
-__device__ __forceinline__ float gemv_act(float v, int act, float slope) {
-  switch (act) {
-    case MI355_ACT_LEAKY: return v > 0.f ? v : v * slope;
-    case MI355_ACT_GELU: return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    case MI355_ACT_SILU: return v / (1.0f + expf(-v));
-    case MI355_ACT_GELU_TANH: return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-    case MI355_ACT_ELU: return v > 0.f ? v : expm1f(v);
-    case MI355_ACT_TANH: return tanhf(v);
-    default: return v;
-  }
-}
-
-// the epilogue of NC complete column sums starting at column n0 (bias, activation, LayerScale, residual, SwiGLU, rotary pair, split destinations),
-// executed by whichever lane holds them
+// the epilogue of NC complete column sums starting at column n0 (linear_common.h's tail, or the rotary pair), executed by whichever lane holds them
 template <int MT, int NC>
 __device__ __forceinline__ void gemv_epilogue(const mi355_gemv_args& a, float (&acc)[NC][MT], const int n0) {
   if (a.glu) {  // columns come in (gate, up) pairs: NC is even on this path
@@ -78,7 +63,7 @@ __device__ __forceinline__ void gemv_epilogue(const mi355_gemv_args& a, float (&
       for (int m = 0; m < MT; ++m) {
         if (m >= a.M) break;
         const float g = acc[c][m] * wg + bg, u = acc[c + 1][m] * wu + bu;
-        a.y[(int64_t)m * a.ldy + (n >> 1)] = (g / (1.0f + expf(-g))) * u * a.out_scale;
+        a.y[(int64_t)m * a.ldy + (n >> 1)] = linear_glu_value(g, u) * a.out_scale;
       }
     }
     return;
@@ -116,10 +101,7 @@ __device__ __forceinline__ void gemv_epilogue(const mi355_gemv_args& a, float (&
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       if (m >= a.M) break;
-      float v = gemv_act(acc[c][m] * ws + bias, a.post_act, a.post_slope) * cs;
-      if (a.res) v += a.res[(int64_t)m * a.ldr + n];
-      if (a.y2 && n >= a.split) store_kv_elem(a.y2, (int64_t)m * a.ldy2 + (n - a.split), v * a.out_scale, a.y2_dtype);  // e.g. q -> y, k|v -> the KV-cache slot
-      else a.y[(int64_t)m * a.ldy + n] = v * a.out_scale;
+      linear_finish_regs(a, m, n, acc[c][m] * ws, bias, cs, [&] { return a.res[(int64_t)m * a.ldr + n]; });
     }
   }
 }
@@ -908,10 +890,7 @@ __global__ __launch_bounds__(256) void gemv1_splitk_old_kernel(const mi355_gemv_
     const int n = n0 + c;
     const float sum = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];   // fixed order: run-to-run identical
     const float ws = a.wscale ? a.wscale[n] * kFp8Unbias : 1.f;
-    float v = gemv_act(sum * ws + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
-    if (a.res) v += a.res[n];
-    if (a.y2 && n >= a.split) store_kv_elem(a.y2, n - a.split, v * a.out_scale, a.y2_dtype);
-    else a.y[n] = v * a.out_scale;
+    linear_finish(a, 0, n, sum * ws);
   }
 }
 
@@ -998,10 +977,7 @@ __global__ __launch_bounds__(256) void gemv1_splitk_kernel(const mi355_gemv_args
     float ews = e_ws;
     asm volatile("" : "+v"(ews));   // keeps the scale's multiply (and with it the load's s_waitcnt) down here instead of hoisted in front of the stream
     const float ws = a.wscale ? ews * kFp8Unbias : 1.f;
-    float v = gemv_act(sum * ws + e_bias, a.post_act, a.post_slope) * e_cs;
-    if (a.res) v += e_res;
-    if (a.y2 && ec >= a.split) store_kv_elem(a.y2, ec - a.split, v * a.out_scale, a.y2_dtype);
-    else a.y[ec] = v * a.out_scale;
+    linear_finish_regs(a, 0, ec, sum * ws, e_bias, e_cs, [&] { return e_res; });
   }
 }
 

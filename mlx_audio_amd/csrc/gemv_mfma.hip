@@ -12,51 +12,17 @@
 //     for bf16 -- the same split conv_gemm runs prefill with -- and 22 for fp16) and laid out in LDS in fragment order
 //     [k step][half][group][row] x 16 bytes, so every ds_read_b128 of a wave covers 512 contiguous bytes: conflict-free;
 //   * the four waves of a workgroup take interleaved k steps of ONE 16-column tile (split-K: N / 16 workgroups x 4 waves keep enough loads in
-//     flight even for N = 1024) and add their 16 x 16 partial tiles through LDS; thread (n = t & 15, m = t >> 4) finishes one output: bias,
-//     activation, LayerScale, residual, SwiGLU pairs, split destinations (q -> buffer, k | v -> KV-cache slot);
+//     flight even for N = 1024) and add their 16 x 16 partial tiles through LDS; thread (n = t & 15, m = t >> 4) finishes one output
+//     (linear_finish / linear_finish_glu of linear_common.h);
 //   * fused LayerNorm / RMSNorm: statistics from the registers the staging loads already hold (one read of x), two-pass numerics.
 // Rows m >= M of the 16-wide MFMA column space alias rows m & 7: their outputs are never read.
 #include <stdlib.h>
-#include "common.h"
+#include "linear_common.h"
 
 namespace {
 
 constexpr int kKC = 2048;   // input columns staged per chunk: 2 images x 8 rows x 2 bytes x kKC = 64 KB of LDS
 constexpr int kD = 8;       // weight prefetch depth in k steps (8 x 32 bytes per lane = 16 KB per wave in flight: a whole K = 2048 slice)
-
-__device__ __forceinline__ float mfma_act(float v, int act, float slope) {
-  switch (act) {
-    case MI355_ACT_LEAKY: return v > 0.f ? v : v * slope;
-    case MI355_ACT_GELU: return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    case MI355_ACT_SILU: return v / (1.0f + expf(-v));
-    case MI355_ACT_GELU_TANH: return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-    case MI355_ACT_ELU: return v > 0.f ? v : expm1f(v);
-    case MI355_ACT_TANH: return tanhf(v);
-    default: return v;
-  }
-}
-
-// hi + lo images of two fp32 values (low half = first value)
-template <bool F16>
-__device__ __forceinline__ void split2(const float a, const float b, uint32_t& hi, uint32_t& lo) {
-  if constexpr (F16) {
-    hi = pack_f16x2(a, b);
-    const float ha = (float)__builtin_bit_cast(_Float16, (uint16_t)(hi & 0xffffu)), hb = (float)__builtin_bit_cast(_Float16, (uint16_t)(hi >> 16));
-    lo = pack_f16x2(a - ha, b - hb);
-  } else {
-    hi = pack_bf16x2(a, b);
-    const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16x2(a - ha, b - hb);
-  }
-}
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma_16(const uint4 a, const uint4 b, const f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 template <bool F16>
 __global__ __launch_bounds__(256) void gemv_mfma_kernel(const mi355_gemv_args a) {
@@ -179,10 +145,10 @@ __global__ __launch_bounds__(256) void gemv_mfma_kernel(const mi355_gemv_args a)
 #pragma unroll
           for (int m = 0; m < 8; ++m) {
             uint4 hi, lo;
-            split2<F16>(xa[j][m].x, xa[j][m].y, hi.x, lo.x);
-            split2<F16>(xa[j][m].z, xa[j][m].w, hi.y, lo.y);
-            split2<F16>(xb[j][m].x, xb[j][m].y, hi.z, lo.z);
-            split2<F16>(xb[j][m].z, xb[j][m].w, hi.w, lo.w);
+            split_hi_lo<F16>(xa[j][m].x, xa[j][m].y, hi.x, lo.x);
+            split_hi_lo<F16>(xa[j][m].z, xa[j][m].w, hi.y, lo.y);
+            split_hi_lo<F16>(xb[j][m].x, xb[j][m].y, hi.z, lo.z);
+            split_hi_lo<F16>(xb[j][m].z, xb[j][m].w, hi.w, lo.w);
             planes[base + m] = hi;
             planes[img + base + m] = lo;
           }
@@ -210,10 +176,10 @@ __global__ __launch_bounds__(256) void gemv_mfma_kernel(const mi355_gemv_args a)
       const int p0 = ((ls * 2 + 0) * 4 + gi) * 8 + (li & 7);
       const int p1 = ((ls * 2 + 1) * 4 + gi) * 8 + (li & 7);
       const uint4 h0 = planes[p0], h1 = planes[p1], l0 = planes[img + p0], l1 = planes[img + p1];
-      acc = mfma_16<F16>(w0, h0, acc);
-      acc = mfma_16<F16>(w1, h1, acc);
-      acc = mfma_16<F16>(w0, l0, acc);
-      acc = mfma_16<F16>(w1, l1, acc);
+      acc = mfma_16x16x32<F16>(w0, h0, acc);
+      acc = mfma_16x16x32<F16>(w1, h1, acc);
+      acc = mfma_16x16x32<F16>(w0, l0, acc);
+      acc = mfma_16x16x32<F16>(w1, l1, acc);
       ++it;
     }
   }
@@ -228,14 +194,10 @@ __global__ __launch_bounds__(256) void gemv_mfma_kernel(const mi355_gemv_args a)
   if (a.glu) {  // rows come in (gate, up) pairs: the even thread of a pair finishes both
     if (i & 1) return;
     const float v1 = (red[0][(i + 1) * 16 + m] + red[1][(i + 1) * 16 + m]) + (red[2][(i + 1) * 16 + m] + red[3][(i + 1) * 16 + m]);
-    const float g = v0 + (a.bias ? a.bias[n] : 0.f), u = v1 + (a.bias ? a.bias[n + 1] : 0.f);
-    a.y[(int64_t)m * a.ldy + (n >> 1)] = (g / (1.0f + expf(-g))) * u * a.out_scale;
+    linear_finish_glu(a, m, n, v0, v1);
     return;
   }
-  float v = mfma_act(v0 + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
-  if (a.res) v += a.res[(int64_t)m * a.ldr + n];
-  if (a.y2 && n >= a.split) store_kv_elem(a.y2, (int64_t)m * a.ldy2 + (n - a.split), v * a.out_scale, a.y2_dtype);
-  else a.y[(int64_t)m * a.ldy + n] = v * a.out_scale;
+  linear_finish(a, m, n, v0);
 }
 
 // ---------------------------------------------------------------------------------------------- streaming variant (no fused norm, any K % 64 == 0)
@@ -308,23 +270,20 @@ __global__ __launch_bounds__(256) void gemv_mfma_stream_kernel(const mi355_gemv_
       }
     }
     uint4 hi, lo;
-    split2<F16>(x0.x, x0.y, hi.x, lo.x);
-    split2<F16>(x0.z, x0.w, hi.y, lo.y);
-    split2<F16>(x1.x, x1.y, hi.z, lo.z);
-    split2<F16>(x1.z, x1.w, hi.w, lo.w);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the previous step's fragment reads are done (in-order LDS queue of the wave)
-    __builtin_amdgcn_wave_barrier();
+    split_hi_lo<F16>(x0.x, x0.y, hi.x, lo.x);
+    split_hi_lo<F16>(x0.z, x0.w, hi.y, lo.y);
+    split_hi_lo<F16>(x1.x, x1.y, hi.z, lo.z);
+    split_hi_lo<F16>(x1.z, x1.w, hi.w, lo.w);
+    wave_lds_fence();   // the previous step's fragment reads are done (in-order LDS queue of the wave)
     win[wave][0][wpiece] = hi;
     win[wave][1][wpiece] = lo;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     const int p0 = (0 * 4 + gi) * 8 + (li & 7), p1 = (1 * 4 + gi) * 8 + (li & 7);
     const uint4 h0 = win[wave][0][p0], h1 = win[wave][0][p1], l0 = win[wave][1][p0], l1 = win[wave][1][p1];
-    acc = mfma_16<F16>(w0, h0, acc);
-    acc = mfma_16<F16>(w1, h1, acc);
-    acc = mfma_16<F16>(w0, l0, acc);
-    acc = mfma_16<F16>(w1, l1, acc);
+    acc = mfma_16x16x32<F16>(w0, h0, acc);
+    acc = mfma_16x16x32<F16>(w1, h1, acc);
+    acc = mfma_16x16x32<F16>(w0, l0, acc);
+    acc = mfma_16x16x32<F16>(w1, l1, acc);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) red[wave][(4 * gi + r) * 16 + li] = acc[r];
@@ -336,14 +295,10 @@ __global__ __launch_bounds__(256) void gemv_mfma_stream_kernel(const mi355_gemv_
   if (a.glu) {
     if (i & 1) return;
     const float v1 = (red[0][(i + 1) * 16 + m] + red[1][(i + 1) * 16 + m]) + (red[2][(i + 1) * 16 + m] + red[3][(i + 1) * 16 + m]);
-    const float g = v0 + (a.bias ? a.bias[n] : 0.f), u = v1 + (a.bias ? a.bias[n + 1] : 0.f);
-    a.y[(int64_t)m * a.ldy + (n >> 1)] = (g / (1.0f + expf(-g))) * u * a.out_scale;
+    linear_finish_glu(a, m, n, v0, v1);
     return;
   }
-  float v = mfma_act(v0 + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
-  if (a.res) v += a.res[(int64_t)m * a.ldr + n];
-  if (a.y2 && n >= a.split) store_kv_elem(a.y2, (int64_t)m * a.ldy2 + (n - a.split), v * a.out_scale, a.y2_dtype);
-  else a.y[(int64_t)m * a.ldy + n] = v * a.out_scale;
+  linear_finish(a, m, n, v0);
 }
 
 // ---------------------------------------------------------------------------------------------- K split over workgroups (no fused norm, K > 2048)
@@ -391,10 +346,10 @@ __global__ __launch_bounds__(256) void gemv_mfma_ksplit_kernel(const mi355_gemv_
           xb = *(const float4*)(p + 4);
         }
         uint4 hi, lo;
-        split2<F16>(xa.x, xa.y, hi.x, lo.x);
-        split2<F16>(xa.z, xa.w, hi.y, lo.y);
-        split2<F16>(xb.x, xb.y, hi.z, lo.z);
-        split2<F16>(xb.z, xb.w, hi.w, lo.w);
+        split_hi_lo<F16>(xa.x, xa.y, hi.x, lo.x);
+        split_hi_lo<F16>(xa.z, xa.w, hi.y, lo.y);
+        split_hi_lo<F16>(xb.x, xb.y, hi.z, lo.z);
+        split_hi_lo<F16>(xb.z, xb.w, hi.w, lo.w);
         planes[base + m] = hi;
         planes[img + base + m] = lo;
       }
@@ -408,10 +363,10 @@ __global__ __launch_bounds__(256) void gemv_mfma_ksplit_kernel(const mi355_gemv_
     if (sl < steps) {
       const int p0 = ((sl * 2 + 0) * 4 + gi) * 8 + (li & 7);
       const int p1 = ((sl * 2 + 1) * 4 + gi) * 8 + (li & 7);
-      acc = mfma_16<F16>(ring[d][0], planes[p0], acc);
-      acc = mfma_16<F16>(ring[d][1], planes[p1], acc);
-      acc = mfma_16<F16>(ring[d][0], planes[img + p0], acc);
-      acc = mfma_16<F16>(ring[d][1], planes[img + p1], acc);
+      acc = mfma_16x16x32<F16>(ring[d][0], planes[p0], acc);
+      acc = mfma_16x16x32<F16>(ring[d][1], planes[p1], acc);
+      acc = mfma_16x16x32<F16>(ring[d][0], planes[img + p0], acc);
+      acc = mfma_16x16x32<F16>(ring[d][1], planes[img + p1], acc);
     }
   }
 #pragma unroll
@@ -435,10 +390,7 @@ __global__ __launch_bounds__(256) void gemv_mfma_ksplit_kernel(const mi355_gemv_
     if (tid == 0) a.split_cnt[tile] = 0;   // leave the ticket zeroed for the next launch
   }
   if (m >= M || n >= a.N) return;
-  float v = mfma_act(v0 + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
-  if (a.res) v += a.res[(int64_t)m * a.ldr + n];
-  if (a.y2 && n >= a.split) store_kv_elem(a.y2, (int64_t)m * a.ldy2 + (n - a.split), v * a.out_scale, a.y2_dtype);
-  else a.y[(int64_t)m * a.ldy + n] = v * a.out_scale;
+  linear_finish(a, m, n, v0);
 }
 
 }  // namespace

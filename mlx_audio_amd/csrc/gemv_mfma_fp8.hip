@@ -10,29 +10,16 @@
 //     it is rounded again), ~16 significant bits in total -- the accuracy of the bf16 hi + lo split the 16-bit kernel uses.  Each term has its own
 //     accumulator (the terms differ by a power of two that cannot ride inside an e4m3 operand); they are combined per 2048-column chunk together with
 //     the chunk's row scale of x, and the row scale of W is applied in the epilogue.  The images live in LDS in fragment order [term][k step][half][group][row] x 8 bytes;
-//   * split-K over the four waves of a workgroup, fused LayerNorm / RMSNorm, bias / activation / LayerScale / residual / SwiGLU / split destinations
-//     exactly as gemv_mfma.hip.
+//   * split-K over the four waves of a workgroup and fused LayerNorm / RMSNorm exactly as gemv_mfma.hip; the epilogue is linear_common.h's.
 // Same contract as the 16-bit matrix-pipe kernel (5..8 rows, K % 64 == 0; a fused norm needs K <= 2048); MI355_GEMV_MFMA_FP8=0 keeps the FMA kernel.
 #include <stdlib.h>
-#include "common.h"
+#include "linear_common.h"
 
 namespace {
 
 constexpr int kKC8 = 2048;  // input columns staged: 4 terms x 8 rows x 1 byte x kKC8 = 64 KB of LDS
 constexpr int kD8 = 8;      // weight prefetch depth in k steps (16 bytes per lane and step)
 constexpr int NT = 4;       // e4m3 terms of the input rows
-
-__device__ __forceinline__ float fp8_act(float v, int act, float slope) {
-  switch (act) {
-    case MI355_ACT_LEAKY: return v > 0.f ? v : v * slope;
-    case MI355_ACT_GELU: return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    case MI355_ACT_SILU: return v / (1.0f + expf(-v));
-    case MI355_ACT_GELU_TANH: return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-    case MI355_ACT_ELU: return v > 0.f ? v : expm1f(v);
-    case MI355_ACT_TANH: return tanhf(v);
-    default: return v;
-  }
-}
 
 // 8 fp32 values -> NT e4m3 terms (8 bytes each); the values are already scaled into the e4m3 range
 __device__ __forceinline__ void split_fp8(float (&v)[8], uint2 (&out)[NT]) {
@@ -252,14 +239,10 @@ __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_arg
     if (a.glu) {  // rows come in (gate, up) pairs: the even thread of a pair finishes both
       if (i & 1) continue;
       const float v1 = ((red[0][(i + 1) * 16 + m] + red[1][(i + 1) * 16 + m]) + (red[2][(i + 1) * 16 + m] + red[3][(i + 1) * 16 + m])) * a.wscale[n + 1];
-      const float g = v0 + (a.bias ? a.bias[n] : 0.f), u = v1 + (a.bias ? a.bias[n + 1] : 0.f);
-      a.y[(int64_t)m * a.ldy + (n >> 1)] = (g / (1.0f + expf(-g))) * u * a.out_scale;
+      linear_finish_glu(a, m, n, v0, v1);
       continue;
     }
-    float v = fp8_act(v0 + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
-    if (a.res) v += a.res[(int64_t)m * a.ldr + n];
-    if (a.y2 && n >= a.split) store_kv_elem(a.y2, (int64_t)m * a.ldy2 + (n - a.split), v * a.out_scale, a.y2_dtype);
-    else a.y[(int64_t)m * a.ldy + n] = v * a.out_scale;
+    linear_finish(a, m, n, v0);
   }
 }
 

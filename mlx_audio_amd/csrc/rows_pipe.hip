@@ -14,48 +14,15 @@
 //                      images of the weights' 16-bit type ALREADY in MFMA fragment order in global memory ("planes": [k step][image][half][group][row] x 16
 //                      bytes), loaded straight into registers -- no LDS staging, no conversion, no barrier in the loop.  The four partial tiles of
 //                      the waves meet in LDS; the workgroup writes ONE fp32 partial tile to slab `kgroup` of the workspace.  No epilogue at all.
-//   mi355_rows_finish  one workgroup per row: sums the K-group slabs in a fixed order (deterministic), then bias / activation / LayerScale /
-//                      residual / SwiGLU / split destinations (q -> buffer, k | v -> KV-cache slot) exactly as mi355_gemv, and -- what makes the
+//   mi355_rows_finish  one workgroup per row: sums the K-group slabs in a fixed order (deterministic), then the tail of mi355_gemv (the arithmetic
+//                      of linear_common.h on this call's own argument struct: its loads and stores stay here), and -- what makes the
 //                      next GEMM's input free -- optionally normalises the finished row (LayerNorm / RMSNorm with REAL row statistics, two-pass) and
 //                      writes it as planes.  With kgroups = 1 it is also the converter fp32 rows -> planes (attention output, step input).
 // Input precision: hi + lo images = ~16 mantissa bits for bf16 weights (~22 for fp16), the split of the prefill GEMMs and of gemv_mfma.hip.
 #include <stdlib.h>
-#include "common.h"
+#include "linear_common.h"
 
 namespace {
-
-__device__ __forceinline__ float pipe_act(float v, int act, float slope) {
-  switch (act) {
-    case MI355_ACT_LEAKY: return v > 0.f ? v : v * slope;
-    case MI355_ACT_GELU: return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    case MI355_ACT_SILU: return v / (1.0f + expf(-v));
-    case MI355_ACT_GELU_TANH: return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-    case MI355_ACT_ELU: return v > 0.f ? v : expm1f(v);
-    case MI355_ACT_TANH: return tanhf(v);
-    default: return v;
-  }
-}
-
-template <bool F16>
-__device__ __forceinline__ void pipe_split2(const float a, const float b, uint32_t& hi, uint32_t& lo) {
-  if constexpr (F16) {
-    hi = pack_f16x2(a, b);
-    const float ha = (float)__builtin_bit_cast(_Float16, (uint16_t)(hi & 0xffffu)), hb = (float)__builtin_bit_cast(_Float16, (uint16_t)(hi >> 16));
-    lo = pack_f16x2(a - ha, b - hb);
-  } else {
-    hi = pack_bf16x2(a, b);
-    const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16x2(a - ha, b - hb);
-  }
-}
-
-template <bool F16>
-__device__ __forceinline__ f32x4 pipe_mfma(const uint4 a, const uint4 b, const f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // ---------------------------------------------------------------------------------------------- the GEMM
 // MR = row groups of 16 in the planes (R = 16 MR rows), T = adjacent column tiles per workgroup.
@@ -117,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(const mi355_rows_gemm
 #pragma unroll
       for (int r = 0; r < MR; ++r)
 #pragma unroll
-        for (int j = 0; j < T; ++j) acc[j][r] = pipe_mfma<F16>(A[j][h], B[im][r], acc[j][r]);
+        for (int j = 0; j < T; ++j) acc[j][r] = mfma_16x16x32<F16>(A[j][h], B[im][r], acc[j][r]);
   };
   int s = s_begin + wave;
   if (s < s_end) {
@@ -161,13 +128,13 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(const mi355_rows_gemm
         }
         if (a.wscale) { gv *= a.wscale[tile * 16 + 2 * e]; uv *= a.wscale[tile * 16 + 2 * e + 1]; }
         if (a.glu_bias) { gv += a.glu_bias[tile * 16 + 2 * e]; uv += a.glu_bias[tile * 16 + 2 * e + 1]; }
-        o[e] = (gv / (1.0f + expf(-gv))) * uv;
+        o[e] = linear_glu_value(gv, uv);
       }
       uint4 hi, lo;
-      pipe_split2<F16>(o[0], o[1], hi.x, lo.x);
-      pipe_split2<F16>(o[2], o[3], hi.y, lo.y);
-      pipe_split2<F16>(o[4], o[5], hi.z, lo.z);
-      pipe_split2<F16>(o[6], o[7], hi.w, lo.w);
+      split_hi_lo<F16>(o[0], o[1], hi.x, lo.x);
+      split_hi_lo<F16>(o[2], o[3], hi.y, lo.y);
+      split_hi_lo<F16>(o[4], o[5], hi.z, lo.z);
+      split_hi_lo<F16>(o[6], o[7], hi.w, lo.w);
       const int p = tile, s = p >> 3, g = (p & 7) >> 1, h = p & 1;
       uint4* const po = (uint4*)a.glu_planes_out;
       po[(((s * 2 + 0) * 2 + h) * 4 + g) * R + m] = hi;
@@ -263,7 +230,7 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(const mi355_rows_finis
       for (int e = 0; e < 8; ++e) {
         const float sg = a.wscale ? a.wscale[2 * (n0 + e)] : 1.f, su = a.wscale ? a.wscale[2 * (n0 + e) + 1] : 1.f;
         const float g = gu[2 * e] * sg + (a.bias ? a.bias[2 * (n0 + e)] : 0.f), u = gu[2 * e + 1] * su + (a.bias ? a.bias[2 * (n0 + e) + 1] : 0.f);
-        w[e] = (g / (1.0f + expf(-g))) * u * a.out_scale;
+        w[e] = linear_glu_value(g, u) * a.out_scale;
       }
     } else {
       float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
@@ -287,7 +254,7 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(const mi355_rows_finis
         const int n = n0 + e;
         float t = 0.f;
         if (n < No) {
-          t = pipe_act(sv[e] * (a.wscale ? a.wscale[n] : 1.f) + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
+          t = linear_act(sv[e] * (a.wscale ? a.wscale[n] : 1.f) + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);
           if (a.res) t += a.res[(int64_t)m * a.ldr + n];
           t *= a.out_scale;
         }
@@ -317,10 +284,10 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(const mi355_rows_finis
     }
     if (pl) {
       uint4 hi, lo;
-      pipe_split2<F16>(t[0], t[1], hi.x, lo.x);
-      pipe_split2<F16>(t[2], t[3], hi.y, lo.y);
-      pipe_split2<F16>(t[4], t[5], hi.z, lo.z);
-      pipe_split2<F16>(t[6], t[7], hi.w, lo.w);
+      split_hi_lo<F16>(t[0], t[1], hi.x, lo.x);
+      split_hi_lo<F16>(t[2], t[3], hi.y, lo.y);
+      split_hi_lo<F16>(t[4], t[5], hi.z, lo.z);
+      split_hi_lo<F16>(t[6], t[7], hi.w, lo.w);
       const int s = p >> 3, g = (p & 7) >> 1, h = p & 1;
       pl[(((s * 2 + 0) * 2 + h) * 4 + g) * a.R + m] = hi;
       pl[(((s * 2 + 1) * 2 + h) * 4 + g) * a.R + m] = lo;
@@ -468,13 +435,13 @@ __global__ __launch_bounds__(256) void rows_finish_lean_kernel(const mi355_rows_
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[it][e] = f(v[it][e]);
     };
-    switch (a.post_act) {
-      case MI355_ACT_LEAKY: each([&](float x) { return x > 0.f ? x : x * a.post_slope; }); break;
-      case MI355_ACT_GELU: each([](float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }); break;
-      case MI355_ACT_SILU: each([](float x) { return x / (1.0f + expf(-x)); }); break;
-      case MI355_ACT_GELU_TANH: each([](float x) { return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x))); }); break;
-      case MI355_ACT_ELU: each([](float x) { return x > 0.f ? x : expm1f(x); }); break;
-      case MI355_ACT_TANH: each([](float x) { return tanhf(x); }); break;
+    switch (a.post_act) {   // linear_act with a constant tag: its own switch folds away inside each case
+      case MI355_ACT_LEAKY: each([&](float x) { return linear_act(x, MI355_ACT_LEAKY, a.post_slope); }); break;
+      case MI355_ACT_GELU: each([](float x) { return linear_act(x, MI355_ACT_GELU, 0.f); }); break;
+      case MI355_ACT_SILU: each([](float x) { return linear_act(x, MI355_ACT_SILU, 0.f); }); break;
+      case MI355_ACT_GELU_TANH: each([](float x) { return linear_act(x, MI355_ACT_GELU_TANH, 0.f); }); break;
+      case MI355_ACT_ELU: each([](float x) { return linear_act(x, MI355_ACT_ELU, 0.f); }); break;
+      case MI355_ACT_TANH: each([](float x) { return linear_act(x, MI355_ACT_TANH, 0.f); }); break;
       default: break;
     }
   }
@@ -538,10 +505,10 @@ __global__ __launch_bounds__(256) void rows_finish_lean_kernel(const mi355_rows_
     }
     if (pl) {
       uint4 hi, lo;
-      pipe_split2<F16>(t[0], t[1], hi.x, lo.x);
-      pipe_split2<F16>(t[2], t[3], hi.y, lo.y);
-      pipe_split2<F16>(t[4], t[5], hi.z, lo.z);
-      pipe_split2<F16>(t[6], t[7], hi.w, lo.w);
+      split_hi_lo<F16>(t[0], t[1], hi.x, lo.x);
+      split_hi_lo<F16>(t[2], t[3], hi.y, lo.y);
+      split_hi_lo<F16>(t[4], t[5], hi.z, lo.z);
+      split_hi_lo<F16>(t[6], t[7], hi.w, lo.w);
       const int s = p >> 3, gg = (p & 7) >> 1, h = p & 1;
       pl[(((s * 2 + 0) * 2 + h) * 4 + gg) * a.R + m] = hi;
       pl[(((s * 2 + 1) * 2 + h) * 4 + gg) * a.R + m] = lo;

@@ -648,6 +648,79 @@ def test_gemv_matrix_pipe(ops, M, N, K, f16, mode, glu, act, use_res, split):
         assert rel_err(y.cpu(), v) < tol, rel_err(y.cpu(), v)
 
 
+_EPI_ACTS = {0: lambda v: v, 1: lambda v: F.leaky_relu(v, 0.1), 3: F.gelu, 4: F.elu, 5: F.silu, 6: lambda v: F.gelu(v, approximate="tanh"), 7: torch.tanh}
+_EPI_N, _EPI_SPLIT, _EPI_PAD = 40, 16, 8   # two full 16-column tiles and a ragged one of 8; y2 takes the columns from 16 on
+_EPI_GUARD = -777.0                        # what the columns past N of y hold before and after a call
+
+
+def _linear_epilogue_cases(ops, M, K, fp8):
+    """Every feature of the shared tail of the decode-side linear kernels (csrc/linear_common.h) through the kernel M rows, K columns and the weight
+    type select: yields (label, stored, expected float64).  The product is computed once per (M, K, fp8) in float64; `stored` is what the call left
+    in y (and, for a split, y | y2 side by side).  The writes outside the destinations are asserted here."""
+    N = _EPI_N
+    g = torch.Generator().manual_seed(1000 * M + K + int(fp8))
+    w = torch.randn(N, K, generator=g) / math.sqrt(K)
+    bias, cs, res = torch.randn(N, generator=g) * 0.1, torch.randn(N, generator=g), torch.randn(M, N + 4, generator=g)[:, :N]
+    x = torch.randn(M, K + 4, generator=g)[:, :K]
+    if fp8:
+        rw, wq = ops.pack_rowmajor_fp8(w, bias, DEV)
+    else:
+        wq = _round16(w, False)
+        rw = ops.pack_rowmajor16(wq, bias, DEV)
+    prod = x.double() @ wq.double().T
+    xd = torch.zeros(M, K + 4, device=DEV)
+    xd[:, :K] = x.to(DEV)
+    xd, csd, resd = xd[:, :K], cs.to(DEV), res.to(DEV)   # strided x and res rows
+
+    def run(n_y, **kw):
+        ybuf = torch.full((M, n_y + _EPI_PAD), _EPI_GUARD, device=DEV)
+        ops.gemv(xd, rw, ybuf[:, :n_y], **kw)
+        torch.cuda.synchronize()
+        assert bool((ybuf[:, n_y:] == _EPI_GUARD).all()), "y was written past its last column"
+        return ybuf[:, :n_y].cpu()
+
+    yield "plain", run(N), prod + bias.double()
+    for act, fn in _EPI_ACTS.items():   # bias, activation, LayerScale, residual and output scale together
+        exp = (fn(prod + bias.double()) * cs.double() + res.double()) * 0.5
+        yield "act%d" % act, run(N, post_act=act, post_slope=0.1, colscale=csd, res=resd, out_scale=0.5), exp
+    if K <= 2048:   # (a SwiGLU image with a longer row is not a one-row split-K shape)
+        v = prod + bias.double()
+        yield "glu", run(N // 2, glu=True, out_scale=0.5), F.silu(v[:, 0::2]) * v[:, 1::2] * 0.5
+    # columns >= 16 into a strided slot of each element type; the 16-bit slots hold the float32 slot's values rounded to nearest even, bit for bit
+    exp = ((prod + bias.double()) * cs.double() + res.double()) * 0.5
+    slots = {}
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        cache = torch.zeros(M, 3, (N - _EPI_SPLIT) + _EPI_PAD, device=DEV, dtype=dt)
+        y = run(_EPI_SPLIT, colscale=csd, res=resd, out_scale=0.5, y2=cache[:, 1, : N - _EPI_SPLIT])
+        slots[dt] = cache[:, 1, : N - _EPI_SPLIT].cpu()
+        slots.setdefault("y", y)
+        assert torch.equal(y, slots["y"]), "the y columns depend on the element type of the y2 slot"
+        assert float(cache[:, 0].abs().max()) == 0.0 and float(cache[:, 2].abs().max()) == 0.0 and float(cache[:, 1, N - _EPI_SPLIT:].abs().max()) == 0.0
+        if dt != torch.float32:
+            assert torch.equal(slots[dt], slots[torch.float32].to(dt)), "16-bit y2 slot != the float32 slot rounded to nearest even (%s)" % dt
+        yield "split_%s" % str(dt).split(".")[-1], torch.cat([y, slots[dt].float()], 1), exp if dt == torch.float32 else None
+
+
+_EPI_KERNELS = [(1, 128, False), (3, 128, False), (8, 128, False), (9, 128, False), (33, 128, False),   # bf16: one-row, gemv_kernel, gemv_mfma, gemm_rows 16 / 64 rows
+                (1, 128, True), (8, 128, True),                                                        # fp8: one-row, fp8 matrix pipe
+                (1, 4096, False)]                                                                      # bf16, long row: gemv1_splitk_kernel
+
+
+@pytest.mark.parametrize("M,K,fp8", _EPI_KERNELS)
+def test_linear_epilogue_matrix(ops, M, K, fp8):
+    """One small matrix (N = 40: two full column tiles and a ragged one; K = 128: two k steps) pushes every feature of the shared tail -- each
+    activation with bias, colscale, res and out_scale = 0.5 on, a plain call, SwiGLU pairs, a split into a strided y2 slot of every element type --
+    through every kernel family that calls it, against float64.  Bars: the ones this file holds each kernel to already (_gemv_tol for the 1..8-row
+    kernels, 2e-5 for bf16 images on gemm_rows, 3e-5 for the fp8 matrix pipe)."""
+    tol = (3e-5 if 5 <= M <= 8 else _gemv_tol(M, K, False)) if fp8 else (2e-5 if M > 8 else _gemv_tol(M, K, False))
+    for label, got, exp in _linear_epilogue_cases(ops, M, K, fp8):
+        if exp is None:   # a 16-bit slot: held bitwise to the float32 slot inside the generator
+            continue
+        err = rel_err(got, exp)
+        print("linear_epilogue M=%d K=%d fp8=%d %-14s rel_err %.3g (bar %.3g)" % (M, K, fp8, label, err, tol))
+        assert err < tol, (label, err, tol)
+
+
 @pytest.mark.parametrize("M,heads,kv_heads,dh,K,fp8", [(1, 4, 1, 64, 256, False), (3, 8, 2, 128, 1024, False), (1, 32, 8, 64, 2048, False), (2, 4, 2, 64, 512, True)])
 def test_gemv_fused_interleaved_rope(ops, M, heads, kv_heads, dh, K, fp8):
     """q | k | v projection with the interleaved rotary embedding (nn.RoPE(traditional=True), sesame/attention.py:41-105) applied in the GEMV
