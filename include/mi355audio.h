@@ -382,6 +382,27 @@ typedef struct {
 int mi355_stencil2d_k3s2(const mi355_stencil2d_k3s2_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sortformer (vad/models/sortformer/sortformer.py): attention of the BART-style Transformer encoder, 8 heads of 24.  One entry
+ * point added to ABI 37 (new struct and function only; no existing layout changed).  Plain float32, a fixed summation order that
+ * does not depend on the launch geometry: two calls on the same bytes give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+/* TransformerAttention.__call__ (sortformer.py:532-564) behind the projections, under TransformerEncoder's key mask (621-631).
+ * Head h sits at columns [h dh, (h + 1) dh) of every row.  With n = lens[b] (NULL: T), for i < n:
+ *   out_i = sum_{j<n} softmax_j(scale * q_i . k_j) v_j;
+ * output rows n <= i < T are written as zeros.  (The reference adds -1e4 to the scores of the keys j >= n; in float32 their
+ * weights underflow to exactly 0 whenever a valid key exists, so hiding them is the same function.)  lens[b] >= 1 is the
+ * caller's duty.  dh 8, 16, 24 or 32; any T >= 1; MI355_ERR_ARG without a launch for any other dh.  Rows 16-byte aligned (strides
+ * multiples of 4).  No [T, T] matrix is written to memory and there is no workspace. */
+typedef struct {
+  const float* q; int64_t q_bstride; int32_t ldq;        /* [B, T, ldq] */
+  const float* k; int64_t k_bstride; int32_t ldk;
+  const float* v; int64_t v_bstride; int32_t ldv;
+  const int32_t* lens; int32_t B; int32_t T; int32_t heads; int32_t dh; float scale;
+  float* out; int64_t out_bstride; int32_t ldo;          /* [B, T, ldo] */
+} mi355_narrow_attention_args;
+int mi355_narrow_attention(const mi355_narrow_attention_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bidirectional LSTM recurrence (the x-projection is a conv_gemm).
  * Replaces the per-time-step Python loops of LSTM._forward_direction/_backward_direction
  * (modules.py:150-240): gates i,f,g,o; c = f*c + i*g; h = o*tanh(c).

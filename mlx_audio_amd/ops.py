@@ -1134,6 +1134,32 @@ def relpos_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch
     return out
 
 
+NARROW_ATTENTION_WIDTHS = (8, 16, 24, 32)
+
+
+def narrow_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, heads: int, dh: int, scale: Optional[float] = None,
+                     lens: Optional[torch.Tensor] = None, check_lens: bool = True):
+    """``out_i = sum_j softmax_j(scale q_i . k_j) v_j`` over ``j < lens[b]`` (``mi355_narrow_attention``): attention for heads of 8 / 16 / 24 / 32
+    at any T (Sortformer's Transformer encoder: 8 heads of 24).  ``q`` / ``k`` / ``v`` / ``out`` channels-last views [B, T, heads * dh] (thirds of
+    a fused buffer or contiguous).  Rows at and beyond ``lens[b]`` come back zero; every ``lens[b]`` must be in ``[1, T]``: checked here with one
+    device read of ``lens``, which a caller that built ``lens`` from host integers it has already checked turns off (``check_lens=False``)."""
+    B, T, C, qbs, ldq = _nlc(q)
+    Bk, Tk, Ck, kbs, ldk = _nlc(k)
+    Bv, Tv, Cv, vbs, ldv = _nlc(v)
+    Bo, To, Co, obs, ldo = _nlc(out)
+    hd = heads * dh
+    assert (Bk, Tk) == (B, T) and (Bv, Tv) == (B, T) and (Bo, To) == (B, T) and min(C, Ck, Cv, Co) >= hd
+    lp = _lens_arg(lens, B)
+    if lens is not None and check_lens:
+        lo, hi = int(lens.min()), int(lens.max())
+        if lo < 1 or hi > T:
+            raise _lib.Mi355Error(f"narrow_attention: lens must lie in [1, T = {T}] (got min {lo}, max {hi})")
+    _lib.call_struct("mi355_narrow_attention", "mi355_narrow_attention_args", _stream(), q=_ptr(q), q_bstride=qbs, ldq=ldq, k=_ptr(k), k_bstride=kbs,
+                     ldk=ldk, v=_ptr(v), v_bstride=vbs, ldv=ldv, lens=lp, B=B, T=T, heads=heads, dh=dh, scale=dh ** -0.5 if scale is None else scale,
+                     out=_ptr(out), out_bstride=obs, ldo=ldo)
+    return out
+
+
 def glu_dwconv_silu(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, *, lens: Optional[torch.Tensor] = None):
     """``silu(b + sum_k w[:, k] * g[t + k - (K - 1) / 2])`` with ``g = x[..., :C] * sigmoid(x[..., C:])`` (``mi355_glu_dwconv_silu``): the middle of the
     Conformer's convolution module, ``x`` [B, L, 2 C] -> ``y`` [B, L, C]; ``w`` [C, K] (K odd, <= ``GLU_DWCONV_MAX_TAPS``) and ``b`` [C] carry the

@@ -263,20 +263,44 @@ class Conformer:
     def __call__(self, mel: torch.Tensor, lengths=None, *, return_layers: bool = False):
         """``return_layers``: a third result, dict(pre_encode, layers [n_layers], attn0, conv0) -- the subsampler's output (after ``xscaling``), every
         layer's output, and layer 0's attention-module and convolution-module outputs (before their residual adds)."""
-        a, dev, prec = self.args, self.device, self.precision
+        x, lens = self.pre_encode(mel, lengths)
+        taps = dict(pre_encode=x.clone()) if return_layers else None
+        out = self.encode(x, lens, return_layers=return_layers, inplace=True)
+        if return_layers:
+            taps.update(out[2])
+            return out[0], out[1], taps
+        return out
+
+    def pre_encode(self, mel: torch.Tensor, lengths=None) -> Tuple[torch.Tensor, List[int]]:
+        """The subsampler alone: mel [B, T, feat_in] -> (embeddings [B, T', d_model] after ``xscaling``, the items' T' as host integers)."""
         mel = torch.as_tensor(mel, dtype=torch.float32)
-        if mel.dim() != 3 or mel.shape[2] != a.feat_in:
-            raise ValueError(f"Conformer: mel must be [B, T, {a.feat_in}], got {tuple(mel.shape)}")
+        if mel.dim() != 3 or mel.shape[2] != self.args.feat_in:
+            raise ValueError(f"Conformer: mel must be [B, T, {self.args.feat_in}], got {tuple(mel.shape)}")
         B, T, _ = mel.shape
         lens0 = [T] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
         if len(lens0) != B or min(lens0) < 1 or max(lens0) > T:
             raise ValueError(f"Conformer: lengths {lens0} do not fit a mel of shape {tuple(mel.shape)}")
-        x, lens = self._pre_encode(mel.to(dev).contiguous(), lens0)
+        return self._pre_encode(mel.to(self.device).contiguous(), lens0)
+
+    def encode(self, x: torch.Tensor, lens, *, return_layers: bool = False, inplace: bool = False):
+        """The layers alone: pre-encoded embeddings ``x`` [B, T', d_model] (what ``_pre_encode`` returns, or a caller's own: a streaming state) and the
+        items' valid frames ``lens`` -> (hidden [B, T', d_model], lengths int32 [B] on the device).  The layers work in place: ``inplace=True`` hands
+        ``x`` over as their buffer, otherwise they run on a copy.  ``return_layers``: a third result, dict(layers, attn0, conv0)."""
+        a, dev, prec = self.args, self.device, self.precision
+        if x.dim() != 3 or x.shape[2] != a.d_model or x.dtype != torch.float32:
+            raise ValueError(f"Conformer.encode: embeddings must be float32 [B, T, {a.d_model}], got {tuple(x.shape)}")
+        lens = [int(v) for v in (lens.reshape(-1).tolist() if isinstance(lens, torch.Tensor) else lens)]
+        if len(lens) != x.shape[0] or min(lens) < 1 or max(lens) > x.shape[1]:
+            raise ValueError(f"Conformer.encode: lengths {lens} do not fit embeddings of shape {tuple(x.shape)}")
+        x = x.to(dev).contiguous()
+        if not inplace:
+            x = x.clone()
+        B = x.shape[0]
         Tp, d, H = x.shape[1], a.d_model, a.n_heads
         dh = d // H
         lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
         tables = self._positions(Tp)
-        taps = dict(pre_encode=x.clone(), layers=[]) if return_layers else None
+        taps = dict(layers=[]) if return_layers else None
         xn, h, mid, qkv, att, pw = self._f(B, Tp, d), self._f(B, Tp, d), self._f(B, Tp, d * a.ff_expansion_factor), self._f(B, Tp, 3 * d), self._f(B, Tp, d), self._f(B, Tp, 2 * d)
         for i, blk in enumerate(self.layers):
             ops.layernorm(x, h, weight=blk["norm_ff1"][0], bias=blk["norm_ff1"][1])
