@@ -921,6 +921,7 @@ int mi355_embed_sum(const mi355_embed_sum_args* a, void* stream);
 
 /* Depthwise conv1d (transpose = 0: y[n] = b + sum_k w[c,k] x[n + k - pad]) or depthwise conv_transpose1d (transpose = 1:
  * y[n] = b + sum over t*stride + k - pad == n of w[c,k] x[t]), channels-last, zero outside [0, lens_in[b]).
+ * `stride` belongs to the transposed conv alone: the plain conv has none, and transpose = 0 with stride > 1 is refused.
  * ConvNeXt dwconv k7 of the Qwen3 codec decoder (speech_tokenizer.py ConvNeXtBlock), Mimi's depthwise upsampler (mimi.py:296-320),
  * SNAC's depthwise convs (codec/models/snac/layers.py:170-181, 209-233). */
 typedef struct {

@@ -270,6 +270,7 @@ extern "C" int mi355_dwconv(const mi355_dwconv_args* ap, void* stream) {
   const mi355_dwconv_args a = *ap;
   MI355_REQUIRE(a.B > 0 && a.Lin > 0 && a.Lout > 0 && a.C > 0 && a.K > 0, "dwconv: bad shape");
   MI355_REQUIRE(!a.transpose || a.stride >= 1, "dwconv: transposed conv needs stride >= 1");
+  MI355_REQUIRE(a.transpose || a.stride <= 1, "dwconv: the plain depthwise conv has no stride (got stride %d); stride belongs to the transposed conv", a.stride);
   MI355_REQUIRE(!a.transpose || (a.dil <= 1 && !a.pre_alpha), "dwconv: dilation / Snake prologue exist for the plain depthwise conv only");
   MI355_REQUIRE(!a.pre_alpha || a.pre_inv, "dwconv: pre_alpha without pre_inv");
   MI355_CLEAR_ERROR();

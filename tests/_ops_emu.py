@@ -146,13 +146,14 @@ def rvq_encode(x, tables, tables_t, c2, margins=False):
 
 def dwconv(x, w, bias, y, *, pad=0, stride=1, transpose=False, lens_in=None, dil=1, pre_alpha=None, pre_inv=None):
     assert lens_in is None
+    assert transpose or stride <= 1, "dwconv: the plain depthwise conv has no stride (mi355_dwconv refuses it)"
     B, Lin, C = x.shape
     Lout, K = y.shape[1], w.shape[1]
     xd = x.double()
     if pre_alpha is not None:
         xd = xd + pre_inv[:C].double() * torch.sin(pre_alpha[:C].double() * xd) ** 2
     if not transpose:
-        rows = torch.arange(Lout)[:, None] * stride + torch.arange(K)[None, :] * dil - pad
+        rows = torch.arange(Lout)[:, None] + torch.arange(K)[None, :] * dil - pad
         ok = (rows >= 0) & (rows < Lin)
         t = torch.where(ok[None, :, :, None], xd[:, rows.clamp(0, Lin - 1)], torch.zeros((), dtype=torch.float64))   # [B, Lout, K, C]
         v = torch.einsum("blkc,ck->blc", t, w.double())
