@@ -2,30 +2,15 @@
 //   align_qk_softmax   cross-attention probabilities of the alignment heads (the flash kernels never materialise them)
 //   align_matrix       standardise over tokens, median filter over frames (reflect padding), mean over heads, negate
 //   dtw                the dynamic-time-warping path (timing.py:52-99), one workgroup per item walking the skewed wavefront
-//   softmax_prob_rows  softmax(logits[r])[token[r]]
+//   softmax_prob_rows  softmax(logits[r])[token[r]]; with one token for every row it is mi355_softmax_prob_at (the decode loop's no-speech probability)
 // Every kernel takes B items with per-item lengths and touches nothing beyond them.
 // A frame whose standard deviation over the tokens is 0 standardises to NaN; the median of a window that holds a NaN is NaN, as np.median's is.
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
 constexpr int kAT = 256;   // threads of the qk / matrix kernels
 constexpr int kTT = 8;     // token rows a qk workgroup holds in LDS
-
-__device__ __forceinline__ float block_max256(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // 8 consecutive key elements -> floats
 template <int KV>
@@ -105,7 +90,7 @@ __global__ __launch_bounds__(kAT) void align_qk_softmax_kernel(const mi355_align
     }
   }
 #pragma unroll
-  for (int r = 0; r < kTT; ++r) mx[r] = block_max256(mx[r], red[r]);
+  for (int r = 0; r < kTT; ++r) mx[r] = block_join_max<4>(wave_max(mx[r]), red[r]);
   float sum[kTT];
 #pragma unroll
   for (int r = 0; r < kTT; ++r) sum[r] = 0.f;
@@ -121,7 +106,7 @@ __global__ __launch_bounds__(kAT) void align_qk_softmax_kernel(const mi355_align
   }
   __syncthreads();   // red is reused
 #pragma unroll
-  for (int r = 0; r < kTT; ++r) sum[r] = block_sum256(sum[r], red[r]);
+  for (int r = 0; r < kTT; ++r) sum[r] = block_join_sum<4>(wave_sum(sum[r]), red[r]);
   for (int f = tid; f < Fb; f += kAT) {
 #pragma unroll
     for (int r = 0; r < kTT; ++r)
@@ -269,31 +254,19 @@ __global__ __launch_bounds__(1024) void dtw_kernel(const mi355_dtw_args a, int64
   }
 }
 
-__global__ __launch_bounds__(1024) void softmax_prob_rows_kernel(const float* logits, int64_t ld, int V, const int32_t* tokens, float* out) {
+// out[r] = softmax(logits[r])[token of row r]: tokens[r], or the scalar `token` for every row when tokens is null
+__global__ __launch_bounds__(1024) void softmax_prob_rows_kernel(const float* logits, int64_t ld, int V, const int32_t* tokens, int token, float* out) {
   __shared__ float red[16];
   const int r = blockIdx.x, tid = threadIdx.x;
   const float* lg = logits + (int64_t)r * ld;
-  const int tk = tokens[r];
+  const int tk = tokens ? tokens[r] : token;
   float mx = -INFINITY;
   for (int v = tid; v < V; v += 1024) mx = fmaxf(mx, lg[v]);
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) mx = fmaxf(mx, red[i]);
+  mx = block_join_max<16>(wave_max(mx), red);
   float s = 0.f;
   for (int v = tid; v < V; v += 1024) s += expf(lg[v] - mx);
-  s = wave_sum(s);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += red[i];
-    out[r] = (tk >= 0 && tk < V) ? expf(lg[tk] - mx) / t : 0.f;
-  }
+  s = block_join_sum<16>(wave_sum(s), red);
+  if (tid == 0) out[r] = (tk >= 0 && tk < V) ? expf(lg[tk] - mx) / s : 0.f;
 }
 
 template <int KV>
@@ -368,7 +341,15 @@ extern "C" int mi355_softmax_prob_rows(const float* logits, int64_t ld, int32_t 
   MI355_REQUIRE(logits && tokens && out, "softmax_prob_rows: null tensor");
   MI355_REQUIRE(R > 0 && V > 0 && ld >= V, "softmax_prob_rows: bad shape");
   MI355_CLEAR_ERROR();
-  hipLaunchKernelGGL(softmax_prob_rows_kernel, dim3(R), dim3(1024), 0, (hipStream_t)stream, logits, ld, (int)V, tokens, out);
+  hipLaunchKernelGGL(softmax_prob_rows_kernel, dim3(R), dim3(1024), 0, (hipStream_t)stream, logits, ld, (int)V, tokens, 0, out);
   MI355_LAUNCH_CHECK("softmax_prob_rows");
+  return MI355_OK;
+}
+
+extern "C" int mi355_softmax_prob_at(const float* logits, int32_t ld, int32_t V, int32_t B, int32_t token, float* out, void* stream) {
+  MI355_REQUIRE(logits && out && B > 0 && V > 0 && token >= 0 && token < V, "softmax_prob_at: bad arguments");
+  MI355_CLEAR_ERROR();
+  hipLaunchKernelGGL(softmax_prob_rows_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, (int64_t)ld, (int)V, (const int32_t*)nullptr, (int)token, out);
+  MI355_LAUNCH_CHECK("softmax_prob_at");
   return MI355_OK;
 }

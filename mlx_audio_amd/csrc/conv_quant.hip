@@ -2,6 +2,7 @@
 // utterance, joined with 0.  Read-only over x: the quantised tensor itself is produced inside the consuming conv's prologue
 // (mi355_conv_gemm_args.pre_fq), with the prologue value of conv_common.h's fq_pre_value in both places.
 #include <algorithm>
+#include "block_reduce.h"
 #include "conv_common.h"
 
 using namespace mi355conv;
@@ -71,18 +72,8 @@ __global__ __launch_bounds__(256) void fq_extrema_kernel(const mi355_fake_quant_
       }
     }
   }
-  nmn = wave_max(nmn);
-  mx = wave_max(mx);
   __shared__ float red[8];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[2 * w] = nmn; red[2 * w + 1] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; ++i) { nmn = fmaxf(nmn, red[2 * i]); mx = fmaxf(mx, red[2 * i + 1]); }
-    // both are >= 0: the integer order of their bit patterns is their float order, and max is order-independent (deterministic atomics)
-    atomicMax((int*)a.minmax + 2 * b, __float_as_int(nmn));
-    atomicMax((int*)a.minmax + 2 * b + 1, __float_as_int(mx));
-  }
+  block_extrema_atomic_max(nmn, mx, red, (int*)a.minmax + 2 * b, false);
 }
 
 // {-min, max} of the prologue's output from per-block, per-channel (min, max) of its INPUT (the producing conv's ext_partial).  Grid (slices, B): a
@@ -124,17 +115,8 @@ __global__ __launch_bounds__(256) void fq_extrema_partials_kernel(const mi355_fa
       }
     }
   }
-  nmn = wave_max(nmn);
-  mx = wave_max(mx);
   __shared__ float red[8];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[2 * w] = nmn; red[2 * w + 1] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; ++i) { nmn = fmaxf(nmn, red[2 * i]); mx = fmaxf(mx, red[2 * i + 1]); }
-    atomicMax((int*)a.minmax + 2 * b, __float_as_int(nmn));      // both >= 0: integer order of the bit patterns = float order
-    atomicMax((int*)a.minmax + 2 * b + 1, __float_as_int(mx));
-  }
+  block_extrema_atomic_max(nmn, mx, red, (int*)a.minmax + 2 * b, false);
 }
 
 }  // namespace

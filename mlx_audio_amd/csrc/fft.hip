@@ -8,7 +8,7 @@
 // im) and are separated with the Hermitian identities, so an n_fft-point real STFT costs half a
 // complex FFT.  A workgroup transforms several frame pairs at once so that all 256 lanes have
 // butterflies even for n_fft = 400.
-#include "common.h"
+#include "block_reduce.h"
 #include "fft_fast.h"
 #include <stdlib.h>
 
@@ -304,10 +304,7 @@ __global__ __launch_bounds__(256) void kaldi_frames_kernel(const mi355_kaldi_fra
   };
   float s = 0.f;
   for (int n = tid; n < a.win; n += 256) s += sample(n);
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / (float)a.win;
+  const float mean = block_join_sum<4>(wave_sum(s), red) / (float)a.win;
   float* out = a.frames + (int64_t)f * a.n_fft;
   for (int n = tid; n < a.n_fft; n += 256) {
     float v = 0.f;

@@ -2,7 +2,7 @@
 // Reference call sites: EncodecConv1d / EncodecConvTranspose1d with norm_type = "time_group_norm"
 // (codec/models/encodec/encodec.py:172-291: nn.GroupNorm(1, C, pytorch_compatible=True) behind every conv of the 48 kHz model),
 // EncodecResnetBlock (:305-337: shortcut_norm(shortcut(x)) + norm2(conv2(...)) -- the two-operand apply).
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -10,14 +10,7 @@ constexpr int kPart = MI355_GN_PART_ELEMS;   // elements per workgroup of the st
 constexpr int kVecPerLane = kPart / 4 / 256; // float4 per lane
 static_assert(kPart % 1024 == 0, "a part is a whole number of float4 per lane");
 
-// 256 lanes -> one value every lane holds; fixed association (DPP wave sums, then the four wave shares in order).  All lanes must call it.
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = wave_sum_fast(v);
-  __syncthreads();   // red may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// The block sums below have a fixed association (DPP wave sums, respectively shuffle sums in float64, then the four wave shares in order).
 
 // Statistics of one part: flat elements [e0, e1) of sample b (the valid rows are contiguous when ldx == C; otherwise the element index is
 // mapped to (row, channel) and read 4 bytes at a time).  The part is read ONCE into registers; sums are taken on deviations from the part's
@@ -68,7 +61,7 @@ __global__ __launch_bounds__(256) void group_norm_stats_kernel(const mi355_group
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < kVecPerLane * 4; ++i) s += ok[i] ? v[i] - pivot : 0.f;
-  s = block_sum_256(s, red);
+  s = block_join_sum<4>(wave_sum_fast(s), red);
   const float dmean = s / (float)n;   // part mean - pivot
   float m2 = 0.f;
 #pragma unroll
@@ -76,20 +69,12 @@ __global__ __launch_bounds__(256) void group_norm_stats_kernel(const mi355_group
     const float d = (v[i] - pivot) - dmean;
     m2 += ok[i] ? d * d : 0.f;
   }
-  m2 = block_sum_256(m2, red);
+  m2 = block_join_sum<4>(wave_sum_fast(m2), red);
   if (tid == 0) {
     double* out = a.partials + (int64_t)b * a.partials_bstride + (int64_t)blockIdx.x * 2;
     out[0] = (double)pivot * (double)n + (double)s;
     out[1] = (double)m2;
   }
-}
-
-__device__ __forceinline__ double block_sum_256_d(double v, double* red) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // One workgroup per sample: merge the partial (sum, M2) pairs in float64 (two sweeps: total -> mean, then Chan's decomposition of the sum of
@@ -110,7 +95,7 @@ __global__ __launch_bounds__(256) void group_norm_coef_kernel(const mi355_group_
   };
   double s = 0.0;
   for (int64_t i = tid; i < npairs; i += 256) s += CONV ? (double)pf[i * 2] : pd[i * 2];
-  const double tot = block_sum_256_d(s, red);
+  const double tot = block_join_sum<4>(wave_sum_d(s), red);
   const double mean = total > 0 ? tot / (double)total : 0.0;
   double m2 = 0.0;
   for (int64_t i = tid; i < npairs; i += 256) {
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(256) void group_norm_coef_kernel(const mi355_group_
     const double c = cnt_of(i), d = si / c - mean;
     m2 += qi + d * d * c;
   }
-  m2 = block_sum_256_d(m2, red);
+  m2 = block_join_sum<4>(wave_sum_d(m2), red);
   const double var = total > 0 ? m2 / (double)total : 0.0;
   const double rstd = 1.0 / sqrt(var + (double)a.eps);
   if (tid == 0 && a.mean_rstd) { a.mean_rstd[b * 2] = (float)mean; a.mean_rstd[b * 2 + 1] = (float)rstd; }

@@ -10,40 +10,17 @@
 // Randomness is explicit: mx.random.categorical(logits) is the Gumbel-max trick, so the caller passes Gumbel(0,1) noise
 // [B, V] (null => arg-max; temperature <= 0 => arg-max of the penalised logits like the reference).  Ties in top-k are
 // resolved towards the lower index (mx.argpartition leaves them unspecified).
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
-constexpr int kT = 1024;
+constexpr int kT = 1024, kNW = kT / 64;
 constexpr int kMaxV = 8192;
 
-__device__ __forceinline__ float blk_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int i = 1; i < kT / 64; ++i) r = fmaxf(r, red[i]);
-  return r;
-}
-__device__ __forceinline__ float blk_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < kT / 64; ++i) r += red[i];
-  return r;
-}
-__device__ __forceinline__ int blk_sum_i(int v, int* red) {
+__device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = 0;
-  for (int i = 0; i < kT / 64; ++i) r += red[i];
-  return r;
+  return v;
 }
 // order-preserving map float -> uint32 (larger float => larger key); -inf maps below every finite value
 __device__ __forceinline__ uint32_t fkey(float f) {
@@ -55,7 +32,6 @@ __global__ __launch_bounds__(kT) void sample_kernel(const mi355_sample_args a) {
   __shared__ float lg[kMaxV];
   __shared__ float red[kT / 64];
   __shared__ int redi[kT / 64];
-  __shared__ int best_i;
   const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
   const float NEG = -INFINITY;
   const float* src = a.logits + (int64_t)b * a.ld;
@@ -87,13 +63,13 @@ __global__ __launch_bounds__(kT) void sample_kernel(const mi355_sample_args a) {
         const uint32_t mask = ~((1u << bit) - 1u);
         int c = 0;
         for (int v = tid; v < V; v += kT) c += (fkey(lg[v]) & mask) == cand ? 1 : 0;  // prefix matches and this bit set
-        c = blk_sum_i(c, redi);
+        c = block_join_sum<kNW>(wave_sum_i(c), redi);
         if (c >= need) prefix = cand; else need -= c;
       }
       // prefix == key of the k-th largest value; `need` of the entries equal to it survive
       int ties = 0;
       for (int v = tid; v < V; v += kT) ties += fkey(lg[v]) == prefix ? 1 : 0;
-      ties = blk_sum_i(ties, redi);
+      ties = block_join_sum<kNW>(wave_sum_i(ties), redi);
       if (ties > need) {
         __syncthreads();
         if (tid == 0) {
@@ -111,10 +87,10 @@ __global__ __launch_bounds__(kT) void sample_kernel(const mi355_sample_args a) {
     if (use_p || a.min_p > 0.f) {
       float mx = NEG;
       for (int v = tid; v < V; v += kT) mx = fmaxf(mx, lg[v]);
-      mx = blk_max(mx, red);
+      mx = block_join_max<kNW>(wave_max(mx), red);
       float s = 0.f;
       for (int v = tid; v < V; v += kT) s += expf(lg[v] - mx);
-      s = blk_sum(s, red);
+      s = block_join_sum<kNW>(wave_sum(s), red);
       const float lse = mx + logf(s);
       bool kill[kMaxV / kT];
 #pragma unroll
@@ -146,30 +122,17 @@ __global__ __launch_bounds__(kT) void sample_kernel(const mi355_sample_args a) {
     for (int v = tid; v < V; v += kT) a.filtered[(int64_t)b * a.ld + v] = lg[v];
   // 5. categorical via Gumbel-max (or arg-max)
   const bool noisy = a.gumbel && a.temperature > 0.f;
-  float bv = NEG;
-  int bi = 0x7fffffff;
+  ArgMax best; best.v = NEG; best.i = 0x7fffffff;
   for (int v = tid; v < V; v += kT) {
-    const float x = noisy ? lg[v] + a.gumbel[(int64_t)b * a.ld + v] : lg[v];
-    if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
+    ArgMax c; c.v = noisy ? lg[v] + a.gumbel[(int64_t)b * a.ld + v] : lg[v]; c.i = v;
+    best = better(best, c);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  __syncthreads();
-  if ((tid & 63) == 0) { red[tid >> 6] = bv; redi[tid >> 6] = bi; }
-  __syncthreads();
+  best = block_argmax<kNW>(best, red, redi);
   if (tid == 0) {
-    for (int i = 1; i < kT / 64; ++i)
-      if (red[i] > bv || (red[i] == bv && redi[i] < bi)) { bv = red[i]; bi = redi[i]; }
-    int tokv = bi;
+    int tokv = best.i;
     if (a.done && a.done[b]) tokv = a.done_token;  // finished rows keep emitting the EOS (qwen3_tts.py:1881-1887)
     a.out[(int64_t)b * a.out_ld] = tokv;
-    best_i = tokv;
   }
-  (void)best_i;
 }
 
 }  // namespace

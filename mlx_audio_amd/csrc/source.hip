@@ -9,7 +9,7 @@
 //  * the 20-point DFTs are evaluated in fp64 (cost is nil) and rounded once, so the atan2 phase
 //    features agree with a correctly-rounded rfft; DC / Nyquist imaginary parts are +0 exactly as
 //    pocketfft (numpy, MLX-CPU) produces them.
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -168,17 +168,7 @@ __global__ __launch_bounds__(256) void sine_merge_kernel(const mi355_sine_source
     // 40 000 workgroups x 4 waves hammering the SAME two words per utterance serialised in L2 (the extrema pass took 1.75 ms against 0.2 ms for the
     // merge pass proper): one pair per workgroup (through the noise buffer, which is done with), and only when it RAISES the stored value -- a maximum
     // only grows, a stale read is a smaller value and merely lets the atomic run
-    nmn = wave_max(nmn);
-    mxv = wave_max(mxv);
-    __syncthreads();
-    if ((tid & 63) == 0) { nzs[2 * (tid >> 6)] = nmn; nzs[2 * (tid >> 6) + 1] = mxv; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int i = 1; i < 4; ++i) { nmn = fmaxf(nmn, nzs[2 * i]); mxv = fmaxf(mxv, nzs[2 * i + 1]); }
-      volatile float* cur = a.quant_ws + 2 * b;
-      if (nmn > cur[0]) atomicMax((int*)a.quant_ws + 2 * b, __float_as_int(nmn));
-      if (mxv > cur[1]) atomicMax((int*)a.quant_ws + 2 * b + 1, __float_as_int(mxv));
-    }
+    block_extrema_atomic_max(nmn, mxv, nzs, (int*)a.quant_ws + 2 * b, true);
   }
 }
 
@@ -521,17 +511,8 @@ __global__ __launch_bounds__(256) void fq_prepare_kernel(const mi355_fake_quant_
       mx = fmaxf(mx, t);
     }
   }
-  nmn = wave_max(nmn);
-  mx = wave_max(mx);
   __shared__ float red[8];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[2 * w] = nmn; red[2 * w + 1] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; ++i) { nmn = fmaxf(nmn, red[2 * i]); mx = fmaxf(mx, red[2 * i + 1]); }
-    atomicMax((int*)a.minmax + 2 * b, __float_as_int(nmn));
-    atomicMax((int*)a.minmax + 2 * b + 1, __float_as_int(mx));
-  }
+  block_extrema_atomic_max(nmn, mx, red, (int*)a.minmax + 2 * b, false);
 }
 
 template <bool VEC>
