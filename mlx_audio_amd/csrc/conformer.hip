@@ -3,15 +3,12 @@
 // (q + v) p^T under one softmax), Convolution.__call__ (conformer.py:79-90: GLU -> depthwise conv -> BatchNorm on running statistics -> SiLU) and
 // the 3 x 3 / stride 2 convs of DwStridingSubsampling (conformer.py:174-207).  All three are plain float32 with a fixed summation order: no atomics,
 // and nothing in the order depends on the launch geometry, so two calls on the same bytes give the same bits.
-#include "common.h"
+#include "attn_tile.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-
 // ---------------------------------------------------------------------------------------------------- relative-position attention
-// flash_attn_kernel's tiling (flash_attn.hip): one workgroup = 128 queries x one head, 4 waves x 32 queries, 32-key stages of K / V through LDS,
-// both contractions on v_mfma_f32_32x32x2_f32 in the transposed orientation (a lane owns ONE query column), online softmax in the log2 domain.
+// The query tile of attn_tile.h (tiling, orientation, key order, log2 domain: stated there) with 32-key stages, plus the position term.
 //
 // The position term.  rel_shift is out[i, j] = bd[i, T - 1 - i + j]: score (i, j) takes the table row of distance i - j, row center - (i - j).
 // For a wave's 32 queries i0 .. i0 + 31 and the stage's 32 keys j0 .. j0 + 31 those are the 63 consecutive rows R0 .. R0 + 62,
@@ -43,10 +40,7 @@ __global__ __launch_bounds__(256) void relpos_attn_kernel(const mi355_relpos_att
   const int q0 = blockIdx.x * 128;
   float* obase = a.out + (int64_t)b * a.out_bstride + h * DH;
   if (q0 >= len) {   // a block of padding rows: zeros
-    for (int e = tid; e < 128 * (DH / 4); e += 256) {
-      const int r = q0 + e / (DH / 4);
-      if (r < a.T) *(float4*)(obase + (int64_t)r * a.ldo + (e % (DH / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    attn_zero_block<DH>(obase, a.ldo, q0, a.T, tid);
     return;
   }
   const int i0 = q0 + wave * 32;
@@ -75,27 +69,9 @@ __global__ __launch_bounds__(256) void relpos_attn_kernel(const mi355_relpos_att
   const float* pbase = a.p + h * DH;
 
   float4 kpre[NLD], vpre[NLD];
-  auto prefetch = [&](int kb) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int e = i * 256 + tid;
-      const int row = e / (DH / 4), c4 = e % (DH / 4);
-      int j = kb + row;
-      j = j < len ? j : len - 1;   // clamp: finite data, masked below
-      kpre[i] = *(const float4*)(kbase + (int64_t)j * a.ldk + c4 * 4);
-      vpre[i] = *(const float4*)(vbase + (int64_t)j * a.ldv + c4 * 4);
-    }
-  };
+  auto prefetch = [&](int kb) { attn_stage_prefetch<DH, NLD>(kpre, vpre, kbase, vbase, a.ldk, a.ldv, kb, len, tid); };
   auto commit = [&](int kb) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int e = i * 256 + tid;
-      const int row = e / (DH / 4), c4 = e % (DH / 4);
-      float* kd = Ks + row * LD + c4 * 4;
-      float* vd = Vs + row * LD + c4 * 4;
-      kd[0] = kpre[i].x; kd[1] = kpre[i].y; kd[2] = kpre[i].z; kd[3] = kpre[i].w;
-      vd[0] = vpre[i].x; vd[1] = vpre[i].y; vd[2] = vpre[i].z; vd[3] = vpre[i].w;
-    }
+    attn_stage_commit<DH, NLD>(Ks, Vs, kpre, vpre, tid);
     // the stage's band of the position table: LDS row x holds table row rlo + x (the last wave's R0 first)
     const int rlo = a.center - (q0 + 96) + kb - 31;
     for (int e = tid; e < kRelBand * (DH / 4); e += 256) {
@@ -108,10 +84,7 @@ __global__ __launch_bounds__(256) void relpos_attn_kernel(const mi355_relpos_att
   };
 
   f32x16 o[NDB];
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  attn_zero(o);
   float m = -INFINITY, lsum = 0.f;
   float* bw = Bs + wave * (64 * 32);
 
@@ -126,73 +99,34 @@ __global__ __launch_bounds__(256) void relpos_attn_kernel(const mi355_relpos_att
     const int x0 = 96 - 32 * wave;
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
-      f32x16 bd;
+      // band row 63 (x = 159 for wave 0) is never read back
+      const f32x16 bd = attn_kq<DH>(Ps + min(x0 + blk * 32 + c, kRelBand - 1) * LD + half, qv);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bd[r] = 0.f;
-      const float* prow = Ps + min(x0 + blk * 32 + c, kRelBand - 1) * LD + half;   // band row 63 (x = 159 for wave 0) is never read back
-#pragma unroll
-      for (int s = 0; s < DH / 2; ++s) bd = __builtin_amdgcn_mfma_f32_32x32x2f32(prow[2 * s], qv[s], bd, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bw[(blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 32 + c] = bd[r];
+      for (int r = 0; r < 16; ++r) bw[(blk * 32 + attn_c_row(r, half)) * 32 + c] = bd[r];
     }
-    // ---- S^T block (32 keys x 32 queries)
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const float* krow = Ks + c * LD + half;
-#pragma unroll
-    for (int s = 0; s < DH / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[2 * s], qu[s], acc, 0, 0, 0);
+    f32x16 acc = attn_kq<DH>(Ks + c * LD + half, qu);   // S^T block (32 keys x 32 queries)
     wave_lds_fence();   // the slab is this wave's own
     // ---- + the skewed position term, mask (only a stage that touches len), online softmax (per-lane query)
     const bool edge = kb + KB > len;
     float bm = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int jj = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int jj = attn_c_row(r, half);
       acc[r] += bw[(jj + 31 - c) * 32 + c];
       if (edge && kb + jj >= len) acc[r] = -INFINITY;
       bm = fmaxf(bm, acc[r]);
     }
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float m_new = fmaxf(m, bm);   // finite: key kb is valid in every stage
-    const float alpha = exp2f(m - m_new);   // m = -inf -> 0
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      acc[r] = exp2f(acc[r] - m_new);   // -inf -> 0
-      ps += acc[r];
-    }
-    lsum = lsum * alpha + ps;
-    m = m_new;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-    // ---- O^T += V^T P^T : step s contracts keys (s&3) + 8*(s>>2) + 4*half, which is where acc[s] lives
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const float* vrow = Vs + ((s & 3) + 8 * (s >> 2) + 4 * half) * LD + c;
-#pragma unroll
-      for (int d = 0; d < NDB; ++d) o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[d * 32], acc[s], o[d], 0, 0, 0);
-    }
+    attn_online_softmax<false>(acc, bm, m, lsum, o);   // key kb is valid in every stage
+    attn_pv(o, acc, Vs, LD, half, c);
   }
 
   if (qi >= a.T) return;
   float* orow = obase + (int64_t)qi * a.ldo;
   if (qi >= len) {   // padding rows inside a block that has valid ones
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int c4 = 0; c4 < 4; ++c4) *(float4*)(orow + d * 32 + 8 * c4 + 4 * half) = make_float4(0.f, 0.f, 0.f, 0.f);
+    attn_store_o<DH>(orow, o, 0.f, half, false);
     return;
   }
-  lsum += __shfl_xor(lsum, 32, 64);
-  const float inv = 1.0f / lsum;
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4)
-      *(float4*)(orow + d * 32 + 8 * c4 + 4 * half) = make_float4(o[d][c4 * 4] * inv, o[d][c4 * 4 + 1] * inv, o[d][c4 * 4 + 2] * inv, o[d][c4 * 4 + 3] * inv);
+  attn_store_o<DH>(orow, o, attn_inv_sum<false>(lsum), half, true);
 }
 
 // ---------------------------------------------------------------------------------------------------- GLU -> depthwise conv -> (BatchNorm) -> SiLU

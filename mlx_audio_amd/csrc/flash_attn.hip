@@ -7,31 +7,20 @@
 //     (tts/models/qwen3_tts/talker.py:307, speech_tokenizer.py transformer, codec/models/mimi/modules/transformer.py:109,
 //     lm/models/llama.py / sesame/attention.py for CSM).
 //
-// Two kernels, both exact-f32 arithmetic (activations in this library are fp32, SURVEY section 8 header):
+// Exact-f32 arithmetic (activations in this library are fp32, SURVEY section 8 header):
 //
-//   flash_attn_kernel<DH>  (Tq > 8): one workgroup = 128 queries x one head, 4 waves x 32 queries.  K / V stream
-//     through LDS in 64-key (DH = 64) / 32-key (DH = 128) stages (register prefetch of the next stage under the MFMAs).  Both contractions run on
-//     v_mfma_f32_32x32x2_f32 in the TRANSPOSED orientation, S^T = K Q^T and O^T += V^T P^T, so that a lane owns ONE
-//     query column (l & 31) of every accumulator: the online-softmax max / sum / rescale are per-lane scalars plus a
-//     single xor-32 exchange between the two half-waves (which hold interleaved key rows of the same query), and the
-//     probabilities feed the second MFMA straight from the accumulator registers -- with the key order of step s
-//     chosen as the C-layout row order ((s&3) + 8*(s>>2) + 4*(lane>>5)) no data movement is needed at all.
-//     LDS rows are padded to DH+1 floats: the A-operand ds_read_b32 of both phases is bank-conflict free.
+//   flash_attn_kernel<DH>  (Tq > 8): the query tile of attn_tile.h (tiling, orientation, key order, visibility rule: stated there) with 64-key
+//     (DH = 64) / 32-key (DH = 128) stages, GQA and packed or head-major K / V.  flash_attn16_kernel<DH, KVT> is the same tile for 16-bit K / V.
 //
 //   attn_decode_kernel<DH> (Tq <= 8, the KV-cache decode step): one workgroup per (query, head, item); its 4 (or, for
 //     more than 256 keys, 16) waves take interleaved 64-key chunks, lanes own keys for q.k (float4 row reads) and own channels for p.V, online
 //     softmax per wave, merged through LDS at the end.  An MFMA tile would be 31/32 idle here; this path is bound by
 //     reading the KV cache once.
-//
-// Visibility of key j for query i of item b (len_q / len_k = valid rows, queries are the LAST len_q positions):
-//   k_start <= j < len_k,  causal: j <= i + (len_k - len_q),  window W > 0: j > i + (len_k - len_q) - W.
-// Invisible keys get probability exactly 0 (the reference adds -1e9 / -inf style masks: identical after softmax).
 #include <stdlib.h>
-#include "common.h"
+#include "attn_tile.h"
+#include "linear_common.h"
 
 namespace {
-
-constexpr float kLog2e = 1.4426950408889634f;
 
 // K / V element types: KVT 0 = float32, 1 = bfloat16, 2 = float16 (mi355_flash_attn_args.kv_dtype = MI355_KV_F32 / MI355_KV_BF16 / MI355_KV_F16).  A 16-bit cache
 // is what the reference keeps (K / V live in the checkpoint dtype: whisper.py:360-361, lm/models/cache.py:104-176) and halves the bytes of the
@@ -68,7 +57,7 @@ __device__ __forceinline__ float4 kv_load4(const typename kv_t<KVT>::type* p) {
 
 template <int DH, int KVT>
 __global__ __launch_bounds__(256) void flash_attn_kernel(const mi355_flash_attn_args a) {
-  using kvp = const typename kv_t<KVT>::type*;
+  static_assert(KVT == 0, "16-bit K / V take flash_attn16_kernel");
   constexpr int KB = DH == 64 ? 64 : 32;  // keys per LDS stage (two padded fp32 tiles must fit 64 KB of static LDS)
   constexpr int LD = DH + 1;   // padded LDS row, floats
   constexpr int NDB = DH / 32; // 32-channel blocks of the output
@@ -89,73 +78,28 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const mi355_flash_attn_
   const int qic = qi < len_q ? qi : len_q - 1;
   const int qpos = qic + qoff;  // absolute position of this lane's query
 
-  // Q fragment: B operand of S^T = K Q^T; step s needs Q[q][2s + half] (pre-scaled, log2 domain)
   float qreg[DH / 2];
-  {
-    const float* qrow = a.q + (int64_t)b * a.q_bstride + (int64_t)qic * a.ldq + h * DH;
-    const float sc = a.scale * kLog2e;
-#pragma unroll
-    for (int s = 0; s < DH / 2; ++s) {
-      const float2 t = *(const float2*)(qrow + 2 * s);
-      qreg[s] = (half ? t.y : t.x) * sc;
-    }
-  }
+  attn_load_q<DH>(qreg, a.q + (int64_t)b * a.q_bstride + (int64_t)qic * a.ldq + h * DH, a.scale * kLog2e, half);
 
-  // key range this workgroup needs
-  int kend = len_k, kbeg = 0;
-  if (a.causal) {
-    const int last_q = (q0 + 127 < len_q ? q0 + 127 : len_q - 1) + qoff;
-    kend = last_q + 1 < len_k ? last_q + 1 : len_k;
-    if (kend < 1) kend = 1;
-  }
-  if (a.window > 0) {
-    kbeg = q0 + qoff - a.window + 1;
-    if (kbeg < 0) kbeg = 0;
-  }
-  const int kstart = a.k_start ? a.k_start[b] : 0;  // left-padded rows: keys before k_start[b] are padding
-  if (kstart > kbeg) kbeg = kstart;
-  kbeg &= ~(KB - 1);
+  int kbeg, kend, kstart;
+  attn_key_range<KB>(a, b, q0, len_q, len_k, kbeg, kend, kstart);
 
   // heads packed inside a row (g * DH) or head-major planes (k_hstride: a head's keys contiguous -- the layout for long key ranges:
   // with rows of 2 * heads * DH floats every key of one head sits 6-8 KB from the next and lands on the same one or two L2 channels)
-  kvp kbase = (kvp)a.k + (int64_t)b * a.k_bstride + (a.k_hstride ? (int64_t)g * a.k_hstride : (int64_t)g * DH);
-  kvp vbase = (kvp)a.v + (int64_t)b * a.v_bstride + (a.v_hstride ? (int64_t)g * a.v_hstride : (int64_t)g * DH);
+  const float* kbase = (const float*)a.k + (int64_t)b * a.k_bstride + (a.k_hstride ? (int64_t)g * a.k_hstride : (int64_t)g * DH);
+  const float* vbase = (const float*)a.v + (int64_t)b * a.v_bstride + (a.v_hstride ? (int64_t)g * a.v_hstride : (int64_t)g * DH);
 
   float4 kpre[NLD], vpre[NLD];
-  auto prefetch = [&](int kb) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int e = i * 256 + tid;
-      const int row = e / (DH / 4), c4 = e % (DH / 4);
-      int j = kb + row;
-      j = j < len_k ? j : len_k - 1;  // clamp: finite data, masked below
-      kpre[i] = kv_load4<KVT>(kbase + (int64_t)j * a.ldk + c4 * 4);
-      vpre[i] = kv_load4<KVT>(vbase + (int64_t)j * a.ldv + c4 * 4);
-    }
-  };
-  auto commit = [&]() {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int e = i * 256 + tid;
-      const int row = e / (DH / 4), c4 = e % (DH / 4);
-      float* kd = Ks + row * LD + c4 * 4;
-      float* vd = Vs + row * LD + c4 * 4;
-      kd[0] = kpre[i].x; kd[1] = kpre[i].y; kd[2] = kpre[i].z; kd[3] = kpre[i].w;
-      vd[0] = vpre[i].x; vd[1] = vpre[i].y; vd[2] = vpre[i].z; vd[3] = vpre[i].w;
-    }
-  };
+  auto prefetch = [&](int kb) { attn_stage_prefetch<DH, NLD>(kpre, vpre, kbase, vbase, a.ldk, a.ldv, kb, len_k, tid); };
 
   f32x16 o[NDB];
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  attn_zero(o);
   float m = -INFINITY, lsum = 0.f;
 
   prefetch(kbeg);
   for (int kb = kbeg; kb < kend; kb += KB) {
     __syncthreads();  // everyone is done reading the previous stage
-    commit();
+    attn_stage_commit<DH, NLD>(Ks, Vs, kpre, vpre, tid);
     __syncthreads();
     if (kb + KB < kend) prefetch(kb + KB);
     if (!wave_active) continue;
@@ -163,68 +107,26 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const mi355_flash_attn_
     for (int sub = 0; sub < KB / 32; ++sub) {
       const int kb32 = kb + sub * 32;
       if (kb32 >= kend) break;
-      // ---- S^T block (32 keys x 32 queries)
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float* krow = Ks + (sub * 32 + (lane & 31)) * LD + half;
-#pragma unroll
-      for (int s = 0; s < DH / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[2 * s], qreg[s], acc, 0, 0, 0);
-      // ---- mask + online softmax (per-lane query)
+      f32x16 acc = attn_kq<DH>(Ks + (sub * 32 + (lane & 31)) * LD + half, qreg);
       float bm = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int j = kb32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        bool vis = j < len_k && j >= kstart;
-        if (a.causal) vis = vis && j <= qpos;
-        if (a.window > 0) vis = vis && j > qpos - a.window;
-        acc[r] = vis ? acc[r] : -INFINITY;
+        acc[r] = attn_visible(a, kb32 + attn_c_row(r, half), len_k, kstart, qpos) ? acc[r] : -INFINITY;
         bm = fmaxf(bm, acc[r]);
       }
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-      const float m_new = fmaxf(m, bm);
-      const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-      const float alpha = exp2f(m - m_safe);  // m = -inf -> 0
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        acc[r] = exp2f(acc[r] - m_safe);  // -inf -> 0
-        ps += acc[r];
-      }
-      lsum = lsum * alpha + ps;
-      m = m_new;
-#pragma unroll
-      for (int d = 0; d < NDB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-      // ---- O^T += V^T P^T : step s contracts keys (s&3) + 8*(s>>2) + 4*half, which is where acc[s] lives
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const float* vrow = Vs + (sub * 32 + (s & 3) + 8 * (s >> 2) + 4 * half) * LD + (lane & 31);
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[d * 32], acc[s], o[d], 0, 0, 0);
-      }
+      attn_online_softmax<true>(acc, bm, m, lsum, o);
+      attn_pv(o, acc, Vs + sub * 32 * LD, LD, half, lane & 31);
     }
   }
 
   if (!wave_active) return;
-  lsum += __shfl_xor(lsum, 32, 64);
-  const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
-  if (qi < len_q) {
-    float* orow = a.out + (int64_t)b * a.out_bstride + (int64_t)qi * a.ldo + h * DH;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 t = make_float4(o[d][c * 4] * inv, o[d][c * 4 + 1] * inv, o[d][c * 4 + 2] * inv, o[d][c * 4 + 3] * inv);
-        *(float4*)(orow + d * 32 + 8 * c + 4 * half) = t;
-      }
-  }
+  const float inv = attn_inv_sum<true>(lsum);
+  if (qi < len_q) attn_store_o<DH>(a.out + (int64_t)b * a.out_bstride + (int64_t)qi * a.ldo + h * DH, o, inv, half, true);
 }
 
 // ---------------------------------------------------------------------------------------------------- 16-bit K / V on the 16-bit matrix pipe
-// flash_attn16_kernel<DH, KVT>: the prefill / encoder kernel when K and V are held in the checkpoint's 16-bit type.  Same tiling, visibility
-// rule and online softmax as flash_attn_kernel, but both contractions run on v_mfma_f32_32x32x16_{bf16,f16} (16 k per instruction at half the
+// flash_attn16_kernel<DH, KVT>: the prefill / encoder kernel when K and V are held in the checkpoint's 16-bit type.  The tile, key range and
+// visibility rule of attn_tile.h, but both contractions run on v_mfma_f32_32x32x16_{bf16,f16} (16 k per instruction at half the
 // issue cost of the fp32 32x32x2: 16x the MACs per cycle):
 //   * K tile [64 keys][DH] goes global -> LDS untouched (16-byte pieces; rows padded by 16 bytes so the A-operand ds_read_b128 is conflict free);
 //     V goes in TRANSPOSED ([DH][64 keys]) because the second contraction is over keys: its A operand needs 8 keys of one channel per lane.
@@ -298,19 +200,8 @@ __global__ __launch_bounds__(256) void flash_attn16_kernel(const mi355_flash_att
     }
   }
 
-  int kend = len_k, kbeg = 0;
-  if (a.causal) {
-    const int last_q = (q0 + 127 < len_q ? q0 + 127 : len_q - 1) + qoff;
-    kend = last_q + 1 < len_k ? last_q + 1 : len_k;
-    if (kend < 1) kend = 1;
-  }
-  if (a.window > 0) {
-    kbeg = q0 + qoff - a.window + 1;
-    if (kbeg < 0) kbeg = 0;
-  }
-  const int kstart = a.k_start ? a.k_start[b] : 0;
-  if (kstart > kbeg) kbeg = kstart;
-  kbeg &= ~(KB - 1);
+  int kbeg, kend, kstart;
+  attn_key_range<KB>(a, b, q0, len_q, len_k, kbeg, kend, kstart);
 
   const uint16_t* kbase = (const uint16_t*)a.k + (int64_t)b * a.k_bstride + (a.k_hstride ? (int64_t)g * a.k_hstride : (int64_t)g * DH);
   const uint16_t* vbase = (const uint16_t*)a.v + (int64_t)b * a.v_bstride + (a.v_hstride ? (int64_t)g * a.v_hstride : (int64_t)g * DH);
@@ -342,10 +233,7 @@ __global__ __launch_bounds__(256) void flash_attn16_kernel(const mi355_flash_att
   };
 
   f32x16 o[NDB];
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  attn_zero(o);
   float m = -INFINITY, lsum = 0.f;
 
   prefetch(kbeg);
@@ -370,7 +258,7 @@ __global__ __launch_bounds__(256) void flash_attn16_kernel(const mi355_flash_att
         acc = mfma32_16<F16>(kf, qh[s], acc);
         acc = mfma32_16<F16>(kf, ql[s], acc);
       }
-      // ---- mask + online softmax (per-lane query).  The VALU work of this section, not the MFMAs, is what bounds the kernel at DH = 64
+      // ---- mask + online softmax (per-lane query), NOT attn_tile.h's shared step.  The VALU work of this section, not the MFMAs, is what bounds the kernel at DH = 64
       // (~10 lane-instructions per (query, key) against one MFMA cycle), so everything that is not needed on an interior block is skipped
       // wave-uniformly: the visibility mask (only blocks that touch len_k / k_start / the causal diagonal / the window edge), the rescale of
       // O (only when some lane's running maximum moved), and exp2 is the bare v_exp_f32 (arguments <= 0: no range handling needed).
@@ -384,11 +272,7 @@ __global__ __launch_bounds__(256) void flash_attn16_kernel(const mi355_flash_att
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int j = kb32 + (r & 3) + 8 * (r >> 2) + 4 * g2;
-          bool vis = j < len_k && j >= kstart;
-          if (a.causal) vis = vis && j <= qpos;
-          if (a.window > 0) vis = vis && j > qpos - a.window;
-          acc[r] = vis ? acc[r] : -INFINITY;
+          acc[r] = attn_visible(a, kb32 + attn_c_row(r, g2), len_k, kstart, qpos) ? acc[r] : -INFINITY;
           bm = fmaxf(bm, acc[r]);
         }
       }
@@ -433,18 +317,9 @@ __global__ __launch_bounds__(256) void flash_attn16_kernel(const mi355_flash_att
   }
 
   if (!wave_active) return;
-  lsum += __shfl_xor(lsum, 32, 64);
+  lsum += __shfl_xor(lsum, 32, 64);   // (its own two lines, as its softmax section is: attn_inv_sum here costs two registers at DH = 64)
   const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
-  if (qi < len_q) {
-    float* orow = a.out + (int64_t)b * a.out_bstride + (int64_t)qi * a.ldo + h * DH;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 t = make_float4(o[d][c * 4] * inv, o[d][c * 4 + 1] * inv, o[d][c * 4 + 2] * inv, o[d][c * 4 + 3] * inv);
-        *(float4*)(orow + d * 32 + 8 * c + 4 * g2) = t;
-      }
-  }
+  if (qi < len_q) attn_store_o<DH>(a.out + (int64_t)b * a.out_bstride + (int64_t)qi * a.ldo + h * DH, o, inv, g2, true);
 }
 
 template <int DH, int NW, int KVT>
@@ -838,19 +713,11 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const mi355_flash_
         for (int u = 0; u < 8; ++u) e[u] = red_o[0][8 * lane + u];
         uint4 hi, lo;
         if (a.planes_dtype == MI355_W_F16) {
-          auto sp2 = [](float x, float y, uint32_t& hh, uint32_t& ll) {
-            hh = pack_f16x2(x, y);
-            const float hx = (float)__builtin_bit_cast(_Float16, (uint16_t)(hh & 0xffffu)), hy = (float)__builtin_bit_cast(_Float16, (uint16_t)(hh >> 16));
-            ll = pack_f16x2(x - hx, y - hy);
-          };
-          sp2(e[0], e[1], hi.x, lo.x); sp2(e[2], e[3], hi.y, lo.y); sp2(e[4], e[5], hi.z, lo.z); sp2(e[6], e[7], hi.w, lo.w);
+          split_hi_lo<true>(e[0], e[1], hi.x, lo.x); split_hi_lo<true>(e[2], e[3], hi.y, lo.y);
+          split_hi_lo<true>(e[4], e[5], hi.z, lo.z); split_hi_lo<true>(e[6], e[7], hi.w, lo.w);
         } else {
-          auto sp2 = [](float x, float y, uint32_t& hh, uint32_t& ll) {
-            hh = pack_bf16x2(x, y);
-            const float hx = __builtin_bit_cast(float, hh << 16), hy = __builtin_bit_cast(float, hh & 0xffff0000u);
-            ll = pack_bf16x2(x - hx, y - hy);
-          };
-          sp2(e[0], e[1], hi.x, lo.x); sp2(e[2], e[3], hi.y, lo.y); sp2(e[4], e[5], hi.z, lo.z); sp2(e[6], e[7], hi.w, lo.w);
+          split_hi_lo<false>(e[0], e[1], hi.x, lo.x); split_hi_lo<false>(e[2], e[3], hi.y, lo.y);
+          split_hi_lo<false>(e[4], e[5], hi.z, lo.z); split_hi_lo<false>(e[6], e[7], hi.w, lo.w);
         }
         const int k = h * DH + 8 * lane;   // column of the attention output row
         const int s = k >> 6, gq = (k & 63) >> 4, hh = (k >> 3) & 1;
@@ -895,10 +762,8 @@ extern "C" int mi355_flash_attention(const mi355_flash_attn_args* ap, void* stre
     // (flash-decoding) when the caller provided the partial-result workspace
     int nsplit = 1;
     if (a.split_ws && a.split_cnt && a.nsplit != 1) {
-      const int blocks = a.Tq * a.heads * a.B;
       // Measured on Whisper's 1500-key cross-attention (96 workgroups): 38.0 us unsplit vs 53.6 us with 3 splits -- the agent-scope fences
       // around the ticket write back the L2, which costs more than the extra CUs bring.  So the split is opt-in (nsplit >= 2), never automatic.
-      (void)blocks;
       if (a.nsplit > 1) nsplit = a.nsplit;
       if (nsplit > 8) nsplit = 8;
       if (nsplit < 1) nsplit = 1;
@@ -939,7 +804,6 @@ extern "C" int mi355_flash_attention(const mi355_flash_attn_args* ap, void* stre
       if (kvt == 1) { MI355_FLASH16_CASE(1) } else { MI355_FLASH16_CASE(2) }
 #undef MI355_FLASH16_CASE
     }
-#undef MI355_FLASH_CASE
   }
   MI355_LAUNCH_CHECK("flash_attention");
   return MI355_OK;

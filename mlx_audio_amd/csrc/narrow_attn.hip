@@ -8,18 +8,15 @@
 // host's duty (the entry point cannot read device memory; ops.narrow_attention checks it).  Output rows >= lens[b] are written as exact zeros,
 // relpos_attention's convention.
 //
-// relpos_attn_kernel's tiling (conformer.hip) without the band term: one workgroup = 128 queries x one head, 4 waves x 32 queries, 32-key stages
-// of K / V through LDS with the next stage's global loads in flight over the current stage's math, both contractions on v_mfma_f32_32x32x2_f32
-// in the transposed orientation (a lane owns ONE query column), online softmax in the log2 domain.  K Q^T takes DH / 2 MFMA steps.  For P V the
-// V^T operand is ONE 32-row block: row d of the block is head dimension d, and the rows d >= DH are never stored.  Row m of an MFMA result
+// The query tile of attn_tile.h (tiling, orientation, key order, log2 domain: stated there) with 32-key stages.  K Q^T takes DH / 2 MFMA steps.
+// For P V the V^T operand is ONE 32-row block: row d of the block is head dimension d, and the rows d >= DH are never stored.  Row m of an MFMA result
 // depends on row m of the A operand alone, so whatever the lanes c >= DH read (the next key's row, the 32-float tail behind the last one: always
 // inside the LDS array) lands only in accumulator rows that nobody reads.  At DH = 24 a quarter of the P V issue slots are idle.
 // Plain float32, a fixed summation order, no atomics, no workspace: two calls on the same bytes give the same bits.
-#include "common.h"
+#include "attn_tile.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kNarrowKB = 32;   // keys per stage
 
 template <int DH>
@@ -37,10 +34,7 @@ __global__ __launch_bounds__(256) void narrow_attn_kernel(const mi355_narrow_att
   const int q0 = blockIdx.x * 128;
   float* obase = a.out + (int64_t)b * a.out_bstride + h * DH;
   if (q0 >= len) {   // a block of padding rows (or lens[b] == 0): zeros
-    for (int e = tid; e < 128 * C4; e += 256) {
-      const int r = q0 + e / C4;
-      if (r < a.T) *(float4*)(obase + (int64_t)r * a.ldo + (e % C4) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    attn_zero_block<DH>(obase, a.ldo, q0, a.T, tid);
     return;
   }
   const int i0 = q0 + wave * 32;
@@ -48,99 +42,45 @@ __global__ __launch_bounds__(256) void narrow_attn_kernel(const mi355_narrow_att
   const bool wave_active = i0 < len;
   const int qic = qi < len ? qi : len - 1;
 
-  // q pre-scaled into the log2 domain: the B operand of K Q^T; step s needs element 2s + half
   float qs[DH / 2];
-  {
-    const float* qrow = a.q + (int64_t)b * a.q_bstride + (int64_t)qic * a.ldq + h * DH;
-    const float sc = a.scale * kLog2e;
-#pragma unroll
-    for (int s = 0; s < DH / 2; ++s) {
-      const float2 t = *(const float2*)(qrow + 2 * s);
-      qs[s] = (half ? t.y : t.x) * sc;
-    }
-  }
+  attn_load_q<DH>(qs, a.q + (int64_t)b * a.q_bstride + (int64_t)qic * a.ldq + h * DH, a.scale * kLog2e, half);
 
   const float* kbase = a.k + (int64_t)b * a.k_bstride + h * DH;
   const float* vbase = a.v + (int64_t)b * a.v_bstride + h * DH;
-  const bool loader = tid < NLD;
-  const int lrow = tid / C4, lc4 = tid % C4;   // lrow < KB for every loader
+  const bool loader = tid < NLD;   // the stage has fewer pieces than the workgroup has threads
 
-  float4 kpre = make_float4(0.f, 0.f, 0.f, 0.f), vpre = kpre;
+  float4 kpre[1] = {make_float4(0.f, 0.f, 0.f, 0.f)}, vpre[1] = {kpre[0]};
   auto prefetch = [&](int kb) {
-    if (loader) {
-      int j = kb + lrow;
-      j = j < len ? j : len - 1;   // clamp: finite data, masked below
-      kpre = *(const float4*)(kbase + (int64_t)j * a.ldk + lc4 * 4);
-      vpre = *(const float4*)(vbase + (int64_t)j * a.ldv + lc4 * 4);
-    }
-  };
-  auto commit = [&]() {
-    if (loader) {
-      float* kd = Ks + lrow * LD + lc4 * 4;
-      float* vd = Vs + lrow * LD + lc4 * 4;
-      kd[0] = kpre.x; kd[1] = kpre.y; kd[2] = kpre.z; kd[3] = kpre.w;
-      vd[0] = vpre.x; vd[1] = vpre.y; vd[2] = vpre.z; vd[3] = vpre.w;
-    }
+    if (loader) attn_stage_prefetch<DH, 1>(kpre, vpre, kbase, vbase, a.ldk, a.ldv, kb, len, tid);
   };
 
-  f32x16 o;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) o[r] = 0.f;
+  f32x16 o[1];
+  attn_zero(o);
   float m = -INFINITY, lsum = 0.f;
 
   prefetch(0);
   for (int kb = 0; kb < len; kb += KB) {
     __syncthreads();   // everyone is done reading the previous stage
-    commit();
+    if (loader) attn_stage_commit<DH, 1>(Ks, Vs, kpre, vpre, tid);
     __syncthreads();
     if (kb + KB < len) prefetch(kb + KB);
     if (!wave_active) continue;
-    // ---- S^T block (32 keys x 32 queries)
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const float* krow = Ks + c * LD + half;
-#pragma unroll
-    for (int s = 0; s < DH / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[2 * s], qs[s], acc, 0, 0, 0);
+    f32x16 acc = attn_kq<DH>(Ks + c * LD + half, qs);   // S^T block (32 keys x 32 queries)
     // ---- mask (only a stage that touches len), online softmax (per-lane query)
     const bool edge = kb + KB > len;
     float bm = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int jj = (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (edge && kb + jj >= len) acc[r] = -INFINITY;
+      if (edge && kb + attn_c_row(r, half) >= len) acc[r] = -INFINITY;
       bm = fmaxf(bm, acc[r]);
     }
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float m_new = fmaxf(m, bm);   // finite: key kb is valid in every stage
-    const float alpha = exp2f(m - m_new);   // m = -inf -> 0
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      acc[r] = exp2f(acc[r] - m_new);   // -inf -> 0
-      ps += acc[r];
-    }
-    lsum = lsum * alpha + ps;
-    m = m_new;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] *= alpha;
-    // ---- O^T += V^T P^T : step s contracts keys (s&3) + 8*(s>>2) + 4*half, which is where acc[s] lives; lane c is head dimension c
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const float* vrow = Vs + ((s & 3) + 8 * (s >> 2) + 4 * half) * LD + c;
-      o = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[0], acc[s], o, 0, 0, 0);
-    }
+    attn_online_softmax<false>(acc, bm, m, lsum, o);   // key kb is valid in every stage
+    attn_pv(o, acc, Vs, LD, half, c);                  // lane c is head dimension c of the one block
   }
 
   if (qi >= a.T) return;
-  float* orow = obase + (int64_t)qi * a.ldo;
-  lsum += __shfl_xor(lsum, 32, 64);
-  const float inv = 1.0f / lsum;   // unused for the padding rows inside a block that has valid ones: zeros
-  // accumulator row (r & 3) + 8 (r >> 2) + 4 half is head dimension d: this lane holds d = 8 c4 + 4 half + 0 .. 3; DH is a multiple of 8
-#pragma unroll
-  for (int c4 = 0; c4 < DH / 8; ++c4)
-    *(float4*)(orow + 8 * c4 + 4 * half) = qi < len ? make_float4(o[c4 * 4] * inv, o[c4 * 4 + 1] * inv, o[c4 * 4 + 2] * inv, o[c4 * 4 + 3] * inv)
-                                                   : make_float4(0.f, 0.f, 0.f, 0.f);
+  // padding rows inside a block that has valid ones: zeros
+  attn_store_o<DH>(obase + (int64_t)qi * a.ldo, o, attn_inv_sum<false>(lsum), half, qi < len);
 }
 
 template <int DH>

@@ -176,6 +176,50 @@ def test_attention_16bit_kv(ops, kvd, Tq, Tk, dh, G, hm, causal):
     assert rel_err(out.cpu(), exp) < (3e-5 if (Tq > 8 and kvd == torch.bfloat16) else 2e-5), rel_err(out.cpu(), exp)
 
 
+@pytest.mark.parametrize("kvd", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("B,Tq,Tk,heads,kvh,dh,causal,window,ragged,pad", [
+    (2, 130, 130, 4, 2, 64, True, 0, True, None),        # crosses a 128-query block and a 64-key stage
+    (1, 97, 300, 2, 1, 128, True, 0, False, None),       # query offset len_k - len_q
+    (1, 200, 200, 2, 2, 64, True, 50, False, None),      # kbeg rounded down to a stage; blocks left of the window
+    (2, 70, 70, 2, 2, 128, False, 0, True, None),
+    (3, 70, 90, 2, 2, 64, True, 0, False, [0, 13, 41]),  # left padding k_start
+])
+def test_flash16_visibility(ops, kvd, B, Tq, Tk, heads, kvh, dh, causal, window, ragged, pad):
+    """The key range and the visibility rule the 16-bit prefill kernel (Tq > 8) shares with the fp32 one (csrc/attn_tile.h): causal offset, window,
+    ragged lens_q / lens_k and left padding, against float64 attention over the same rounded K / V at test_attention_16bit_kv's bars."""
+    g = torch.Generator().manual_seed(211 + Tq * 7 + Tk + heads + dh)
+    q = torch.randn(B, Tq, heads * dh, generator=g)
+    k = torch.randn(B, Tk, kvh * dh, generator=g).to(kvd)
+    v = torch.randn(B, Tk, kvh * dh, generator=g).to(kvd)
+    lens_q = lens_k = None
+    if ragged:
+        lens_k = torch.tensor([max(1, Tk - 13 * i) for i in range(B)], dtype=torch.int32)
+        lens_q = torch.tensor([min(Tq, int(lens_k[i])) - (i % 2) * 2 for i in range(B)], dtype=torch.int32)
+    scale = 1.0 / math.sqrt(dh)
+    out = torch.full((B, Tq, heads * dh), 7.0, device=DEV)
+    ops.flash_attention(q.to(DEV), k.to(DEV), v.to(DEV), out, heads=heads, kv_heads=kvh, dh=dh, scale=scale, causal=causal, window=window,
+                        lens_q=None if lens_q is None else lens_q.to(DEV), lens_k=None if lens_k is None else lens_k.to(DEV),
+                        k_start=None if pad is None else torch.tensor(pad, dtype=torch.int32, device=DEV))
+    torch.cuda.synchronize()
+    got = out.cpu()
+    bar = 3e-5 if kvd == torch.bfloat16 else 2e-5
+    if pad is None:
+        exp = ref_attention(q, k.float(), v.float(), heads, kvh, dh, scale, causal, window, lens_q, lens_k)
+    for b in range(B):
+        if pad is None:
+            lq = int(lens_q[b]) if lens_q is not None else Tq
+            want, have = exp[b, :lq], got[b, :lq]
+            assert torch.all(got[b, lq:] == 7.0), "rows past lens_q must not be written"
+        else:  # the rows test_attention_left_padded_batch compares: queries inside the padding have no meaning in the reference either
+            p = pad[b]
+            nq = min(Tq, Tk - p)
+            want = ref_attention(q[b:b + 1, Tq - nq:], k[b:b + 1, p:].float(), v[b:b + 1, p:].float(), heads, kvh, dh, scale, causal, window, None, None)[0]
+            have = got[b, Tq - nq:]
+        err = rel_err(have, want)
+        print(f"flash16 visibility {kvd} item {b}: rel err {err:.3e} (bar {bar:.0e})")
+        assert err < bar, (b, err)
+
+
 @pytest.mark.parametrize("dh,H,G,Tk,mode,norms,kvd", [(128, 16, 8, 37, 0, True, torch.float32), (128, 8, 2, 1, 0, True, torch.float32),
                                                       (64, 8, 8, 300, 1, False, torch.float32), (128, 4, 2, 700, 0, True, torch.bfloat16),
                                                       (64, 4, 1, 65, 0, True, torch.float16)])
