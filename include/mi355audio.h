@@ -1140,6 +1140,90 @@ int64_t mi355_dtw_ws_bytes(int32_t N, int32_t M, int32_t B);
 /* out[r] = softmax(logits[r, 0:V])[tokens[r]] with a per-row token id (timing.py:135-139); a token outside [0, V) gives 0 without a read. */
 int mi355_softmax_prob_rows(const float* logits, int64_t ld, int32_t V, int32_t R, const int32_t* tokens, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Unidirectional GRU over whole sequences with MLX nn.GRU semantics (the GRU behind SqueezedGRU, sts/models/deepfilternet/network.py:153-192).
+ * One entry point added to ABI 37 (new struct and function only; no existing layout changed).  One persistent workgroup per sequence, the
+ * recurrent weights resident on the CU (gru.hip).  xproj [B, T, 3H] = x @ Wx^T + b for all steps (the caller's GEMM), gate blocks r | z | n
+ * (PyTorch's bias_hh r / z parts folded into b).  With h_{-1} = h0[b] (NULL: zeros), for t < n = lens[b] (NULL: T; clamped to [0, T]):
+ *   r = sigmoid(x_r + (Wh h)_r),  z = sigmoid(x_z + (Wh h)_z),  n = tanh(x_n + r * ((Wh h)_n + bhn)),  h = (1 - z) * n + z * h,  out[b, t] = h;
+ * output rows n <= t < T are written as zeros; hT[b] (nullable) receives the state after step n (h0[b] when n = 0).
+ * wh: IEEE-half image of Wh / wh_scale [3H, H] as 16-byte groups [H / 8][3H][8] (group (kg, row) = Wh[row, 8 kg .. 8 kg + 8)), 16-byte aligned;
+ * wh_scale a power of two (0 = 1) that multiplies every recurrent sum (the scheme of mi355_lstm_args.wh_scale).  fp32 accumulation in a fixed
+ * order: two calls on the same bytes give the same bits.  H 64, 128 or 256; MI355_ERR_UNSUPPORTED without a launch for any other H.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* xproj; int64_t xproj_bstride; int32_t ld_xproj;   /* [B, T, ld_xproj], ld_xproj >= 3H */
+  const uint16_t* wh; float wh_scale;
+  const float* bhn;                                              /* [H] */
+  const float* h0;                                               /* [B, H] nullable => zeros */
+  const int32_t* lens;                                           /* [B] nullable => T */
+  int32_t B; int32_t T; int32_t H;
+  float* out; int64_t out_bstride; int32_t ld_out;               /* [B, T, ld_out], ld_out >= H */
+  float* hT;                                                     /* [B, H] nullable */
+} mi355_gru_seq_args;
+int mi355_gru_seq(const mi355_gru_seq_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * DeepFilterNet2 / 3 (sts/models/deepfilternet): the feature front end, the fused conv block and the mask + deep-filter back end (dfn.hip).
+ * Three entry points added to ABI 37 (new structs and functions only).  Plain float32 in the reference's operation order (no contraction), every
+ * output element a fixed sum: two calls on the same bytes give the same bits.  Spectra are interleaved (re, im) float pairs [B, T, F, 2]; the
+ * activations are channels-last [B, T, F, C] and contiguous behind their batch stride.  lens [B] nullable (then T), clamped to [0, T].
+ * ------------------------------------------------------------------------------------------ */
+#define MI355_DFN_MAX_BANDS 256   /* nb_erb and nb_df of mi355_dfn_features */
+#define MI355_DFN_MAX_CH 64       /* channels on either side of mi355_dfn_conv2d */
+/* model.py:306-323,366-410 + DfNet._apply_lookahead (network.py:759-773).  spec_out = spec * wnorm (all F bins); per frame the ERB energies of
+ * |spec_out|^2 -- erb_fb [F, E] given: the filterbank product; NULL: the mean over band e's bins [erb_start[e], erb_start[e + 1]) --, then
+ * 10 log10(. + 1e-10) and the two running normalisations  state = x * one_minus_alpha + state * alpha  (states start at linspace(-60, -90, E) and
+ * linspace(0.001, 0.0001, D), x = the dB value / |spec_out| of bin d < D): erb = (x - state) / 40, df = spec_out / sqrt(state).  With n = lens[b]:
+ * feat[t] = norm[t + la] for t + la < n, zeros for the rest of [0, T) (la = lookahead if n > lookahead else 0: the reference skips the shift).
+ * Two launches: the band energies per (frame, item) in parallel (the dB values pass through feat_erb), then the two recurrences, one thread per
+ * band / bin, sequential over the item's frames.  E, D <= MI355_DFN_MAX_BANDS, D <= F. */
+typedef struct {
+  const float* spec; int64_t spec_bstride;            /* [B, T, F, 2] */
+  float wnorm; float alpha; float one_minus_alpha;
+  const float* erb_fb; const int32_t* erb_start;      /* [F, E] or [E + 1] (device); exactly one is given */
+  const int32_t* lens; int32_t B; int32_t T; int32_t F; int32_t E; int32_t D; int32_t lookahead;
+  float* spec_out; int64_t spec_out_bstride;          /* [B, T, F, 2] (may alias spec) */
+  float* feat_erb; float* feat_df;                    /* [B, T, E] and [B, T, D, 2], contiguous */
+} mi355_dfn_features_args;
+int mi355_dfn_features(const mi355_dfn_features_args* a, void* stream);
+
+/* The fused conv block (network.py:249-319,357-417,478-556,559-649), x [B, T, F, Cin] -> y [B, T, Fo, Cout]:
+ *   mid = conv(x) with w in the PyTorch layout -- [Cmid, Cin / groups, kt, kf] (Conv2d) or, transposed = 1, [Cin, Cmid / groups, kt, kf]
+ *         (ConvTranspose2d), kt <= 5, kf 1 or 3; time: kt - 1 - lookahead zero frames on the left, lookahead on the right, frames at and beyond
+ *         lens[b] read as zero (transposed: padding kt - 1, i.e. frame t + kt - 1 - k under tap k); frequency: padding kf / 2 at fstride 1 or 2
+ *         (Fo = (F + 2 (kf / 2) - kf) / fstride + 1), or transposed at stride fstride with padding kf / 2 and output padding kf / 2
+ *         (Fo = (F - 1) fstride + kf - kf / 2);
+ *   v   = pw [Cout, Cmid] @ mid when pw is given (else Cout = Cmid, v = mid);
+ *   y   = act(v * scale[c] + shift[c]) + add   (scale / shift: the folded BatchNorm, nullable => 1 / 0; act 0 none, 1 ReLU, 2 sigmoid;
+ *         add [B, T, Fo, Cout] nullable, added AFTER the activation).
+ * Output frames at and beyond lens[b] are zeros.  One read of x and one write of y. */
+typedef struct {
+  const float* x; int64_t x_bstride;
+  const float* w; const float* pw; const float* scale; const float* shift;
+  const float* add; int64_t add_bstride;
+  const int32_t* lens;
+  int32_t B; int32_t T; int32_t F; int32_t Cin; int32_t Cmid; int32_t Cout; int32_t groups;
+  int32_t kt; int32_t kf; int32_t lookahead; int32_t fstride; int32_t transposed; int32_t act;
+  float* y; int64_t y_bstride;
+} mi355_dfn_conv2d_args;
+int mi355_dfn_conv2d(const mi355_dfn_conv2d_args* a, void* stream);
+int32_t mi355_dfn_conv2d_fo(int32_t F, int32_t kf, int32_t fstride, int32_t transposed);
+
+/* Mask, deep filter and assembly (network.py:671-736,786-804; model.py:329-333).  gain[t, f] = sum_e m[b, t, e] erb_inv_fb[e, f];
+ * df[t, f] = sum_k S[t + k - (order - 1 - df_lookahead), f] * coef[b, t, f, k] (complex; frames outside [0, lens[b]) are zero) for f < D, where
+ * S = spec * gain when mask_first = 1 (enc_concat: the filter sees the masked spectrum) and S = spec otherwise;
+ * out = (f < D ? df : spec * gain) / wnorm; frames at and beyond lens[b] are zeros. */
+typedef struct {
+  const float* spec; int64_t spec_bstride;            /* [B, T, F, 2] */
+  const float* m; const float* erb_inv_fb;            /* [B, T, E] contiguous; [E, F] */
+  const float* coef;                                  /* [B, T, D, order, 2] contiguous */
+  const int32_t* lens; int32_t B; int32_t T; int32_t F; int32_t E; int32_t D; int32_t order; int32_t df_lookahead; int32_t mask_first;
+  float wnorm;
+  float* out; int64_t out_bstride;                    /* [B, T, F, 2] */
+} mi355_dfn_apply_args;
+int mi355_dfn_apply(const mi355_dfn_apply_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

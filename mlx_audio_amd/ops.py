@@ -408,6 +408,140 @@ def lstm_seq(xproj: torch.Tensor, wh: RowMajor16, out: torch.Tensor, h0: Optiona
     return h, c
 
 
+GRU_SEQ_HIDDEN = (64, 128, 256)
+
+
+@dataclass
+class GruWh:
+    """Recurrent weights of ``gru_seq``: ``w`` the IEEE-half image of Wh / scale ([H/8][3H] 16-byte groups), ``scale`` a power of two."""
+    w: torch.Tensor
+    scale: float
+    h: int
+
+
+def round_gru_wh(wh: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """(the float32 values the 16-bit image of ``wh`` holds, k): wh * 2^k rounded to IEEE half (nearest even) with 2^k the largest power of two that keeps
+    the largest magnitude at or below 32768 -- the scheme of ``pack_lstm_wh_scaled``, except that float32 checkpoints are ROUNDED to half's 11 significant
+    bits rather than refused.  fp16- or bf16-representable values no smaller than 2^-28 of the largest magnitude are held exactly."""
+    w = wh.detach().to(torch.float32).cpu()
+    amax = float(w.abs().max())
+    if not math.isfinite(amax):
+        raise ValueError("gru: non-finite recurrent weights")
+    k = int(math.floor(math.log2(32768.0 / amax))) if amax > 0.0 else 0
+    k = max(-126, min(126, k))
+    return (w * (2.0 ** k)).to(torch.float16).to(torch.float32) * (2.0 ** -k), k
+
+
+def pack_gru_wh(wh: torch.Tensor, device) -> GruWh:
+    """Recurrent weights ``Wh`` [3H, H] (gate blocks r | z | n, the layout of MLX nn.GRU and of PyTorch's weight_hh) for ``gru_seq``."""
+    h3, h = wh.shape
+    assert h3 == 3 * h and h % 8 == 0, wh.shape
+    wr, k = round_gru_wh(wh)
+    img = (wr * (2.0 ** k)).to(torch.float16).view(h3, h // 8, 8).permute(1, 0, 2).contiguous()   # exact: already half values
+    return GruWh(img.view(torch.int16).reshape(-1).to(device), 2.0 ** -k, h)
+
+
+def gru_seq(xproj: torch.Tensor, wh: GruWh, bhn: torch.Tensor, out: torch.Tensor, *, h0: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None,
+            return_state: bool = False):
+    """Unidirectional GRU recurrence over whole sequences (``mi355_gru_seq``, MLX nn.GRU semantics): ``xproj`` [B, T, 3H] = x @ Wx^T + b (gate blocks
+    r | z | n), ``wh`` from ``pack_gru_wh``, ``bhn`` [H], ``out`` [B, T, H]; both may be column views of wider buffers.  ``h0`` [B, H] (default zeros);
+    rows at and beyond ``lens[b]`` are written as zeros.  ``return_state``: also returns the state after step ``lens[b]`` [B, H]."""
+    B, T, H3 = xproj.shape
+    H = wh.h
+    assert H3 == 3 * H and out.shape == (B, T, H) and xproj.stride(2) == 1 and out.stride(2) == 1 and xproj.dtype == out.dtype == torch.float32
+    assert bhn.shape == (H,) and bhn.dtype == torch.float32 and bhn.is_contiguous()
+    assert h0 is None or (h0.shape == (B, H) and h0.dtype == torch.float32 and h0.is_contiguous())
+    hT = torch.empty((B, H), dtype=torch.float32, device=xproj.device) if return_state else None
+    _lib.call_struct("mi355_gru_seq", "mi355_gru_seq_args", _stream(), xproj=_ptr(xproj), xproj_bstride=xproj.stride(0), ld_xproj=xproj.stride(1),
+                     wh=_ptr(wh.w), wh_scale=float(wh.scale), bhn=_ptr(bhn), h0=_ptr(h0), lens=_lens_arg(lens, B), B=B, T=T, H=H,
+                     out=_ptr(out), out_bstride=out.stride(0), ld_out=out.stride(1), hT=_ptr(hT))
+    return (out, hT) if return_state else out
+
+
+# --------------------------------------------------------------------------------------- DeepFilterNet (dfn.hip)
+DFN_MAX_BANDS, DFN_MAX_CH = 256, 64   # MI355_DFN_MAX_BANDS / MI355_DFN_MAX_CH
+DFN_ACT_NONE, DFN_ACT_RELU, DFN_ACT_SIGMOID = 0, 1, 2
+
+
+def _spec4(t: torch.Tensor):
+    assert t.dim() == 4 and t.shape[3] == 2 and t.dtype == torch.float32 and t[0].is_contiguous(), (t.shape, t.stride(), t.dtype)
+    return t.stride(0)
+
+
+def dfn_features(spec: torch.Tensor, *, wnorm: float, alpha: float, one_minus_alpha: float, nb_erb: int, nb_df: int, lookahead: int = 0,
+                 erb_fb: Optional[torch.Tensor] = None, erb_start: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None):
+    """spec [B, T, F, 2] (re, im) -> (spec * wnorm [B, T, F, 2], feat_erb [B, T, E, 1], feat_df [B, T, D, 2]) (``mi355_dfn_features``): the ERB energies
+    (``erb_fb`` [F, E], or band means over ``erb_start`` [E + 1] int32), 10 log10, both running normalisations and the look-ahead shift per item."""
+    B, T, F, _ = spec.shape
+    sbs = _spec4(spec)
+    assert (erb_fb is None) != (erb_start is None)
+    assert erb_fb is None or (erb_fb.shape == (F, nb_erb) and erb_fb.is_contiguous() and erb_fb.dtype == torch.float32)
+    assert erb_start is None or (erb_start.shape == (nb_erb + 1,) and erb_start.dtype == torch.int32 and erb_start.is_contiguous())
+    out = torch.empty((B, T, F, 2), dtype=torch.float32, device=spec.device)
+    fe = torch.empty((B, T, nb_erb, 1), dtype=torch.float32, device=spec.device)
+    fd = torch.empty((B, T, nb_df, 2), dtype=torch.float32, device=spec.device)
+    _lib.call_struct("mi355_dfn_features", "mi355_dfn_features_args", _stream(), spec=_ptr(spec), spec_bstride=sbs, wnorm=float(wnorm), alpha=float(alpha),
+                     one_minus_alpha=float(one_minus_alpha), erb_fb=_ptr(erb_fb), erb_start=_ptr(erb_start), lens=_lens_arg(lens, B), B=B, T=T, F=F,
+                     E=nb_erb, D=nb_df, lookahead=lookahead, spec_out=_ptr(out), spec_out_bstride=out.stride(0), feat_erb=_ptr(fe), feat_df=_ptr(fd))
+    return out, fe, fd
+
+
+@dataclass
+class DfnConv:
+    """One fused conv block of ``dfn_conv2d``: the conv weight in its PyTorch layout ([Cmid, Cin / groups, kt, kf], or [Cin, Cmid / groups, kt, kf] when
+    ``transposed``), the optional pointwise [Cout, Cmid], the BatchNorm folded to ``scale`` / ``shift`` [Cout], the activation."""
+    w: torch.Tensor
+    cin: int
+    cmid: int
+    cout: int
+    groups: int
+    kt: int
+    kf: int
+    fstride: int = 1
+    transposed: bool = False
+    lookahead: int = 0
+    pw: Optional[torch.Tensor] = None
+    scale: Optional[torch.Tensor] = None
+    shift: Optional[torch.Tensor] = None
+    act: int = DFN_ACT_NONE
+
+
+def dfn_conv2d_fo(F: int, kf: int, fstride: int, transposed: bool) -> int:
+    return (F - 1) * fstride + kf - kf // 2 if transposed else (F + 2 * (kf // 2) - kf) // fstride + 1
+
+
+def dfn_conv2d(x: torch.Tensor, cv: DfnConv, *, add: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, T, F, Cin] -> act(BN(pw(conv(x)))) + add, [B, T, Fo, Cout] (``mi355_dfn_conv2d``); frames at and beyond ``lens`` read as zero and are
+    written as zeros."""
+    B, T, F, C = x.shape
+    assert C == cv.cin and x.dtype == torch.float32 and x[0].is_contiguous()
+    Fo = dfn_conv2d_fo(F, cv.kf, cv.fstride, cv.transposed)
+    y = torch.empty((B, T, Fo, cv.cout), dtype=torch.float32, device=x.device)
+    if add is not None:
+        assert add.shape == y.shape and add.dtype == torch.float32 and add[0].is_contiguous()
+    _lib.call_struct("mi355_dfn_conv2d", "mi355_dfn_conv2d_args", _stream(), x=_ptr(x), x_bstride=x.stride(0), w=_ptr(cv.w), pw=_ptr(cv.pw),
+                     scale=_ptr(cv.scale), shift=_ptr(cv.shift), add=_ptr(add), add_bstride=0 if add is None else add.stride(0), lens=_lens_arg(lens, B),
+                     B=B, T=T, F=F, Cin=cv.cin, Cmid=cv.cmid, Cout=cv.cout, groups=cv.groups, kt=cv.kt, kf=cv.kf, lookahead=cv.lookahead,
+                     fstride=cv.fstride, transposed=int(cv.transposed), act=cv.act, y=_ptr(y), y_bstride=y.stride(0))
+    return y
+
+
+def dfn_apply(spec: torch.Tensor, m: torch.Tensor, erb_inv_fb: torch.Tensor, coef: torch.Tensor, *, order: int, df_lookahead: int, mask_first: bool,
+              wnorm: float, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """spec [B, T, F, 2], mask m [B, T, E], ``erb_inv_fb`` [E, F], coef [B, T, D, order, 2] -> the enhanced spectrum / wnorm as complex64 [B, T, F]
+    (``mi355_dfn_apply``): the layout ``istft_frames`` takes."""
+    B, T, F, _ = spec.shape
+    sbs = _spec4(spec)
+    E, D = erb_inv_fb.shape[0], coef.shape[2]
+    assert m.shape[:2] == (B, T) and m.numel() == B * T * E and m.is_contiguous() and erb_inv_fb.shape == (E, F) and erb_inv_fb.is_contiguous()
+    assert coef.shape == (B, T, D, order, 2) and coef.is_contiguous() and m.dtype == coef.dtype == erb_inv_fb.dtype == torch.float32
+    out = torch.empty((B, T, F, 2), dtype=torch.float32, device=spec.device)
+    _lib.call_struct("mi355_dfn_apply", "mi355_dfn_apply_args", _stream(), spec=_ptr(spec), spec_bstride=sbs, m=_ptr(m), erb_inv_fb=_ptr(erb_inv_fb),
+                     coef=_ptr(coef), lens=_lens_arg(lens, B), B=B, T=T, F=F, E=E, D=D, order=order, df_lookahead=df_lookahead, mask_first=int(bool(mask_first)),
+                     wnorm=float(wnorm), out=_ptr(out), out_bstride=out.stride(0))
+    return torch.view_as_complex(out)
+
+
 # --------------------------------------------------------------------------------------- conv / linear
 def conv_gemm(x: torch.Tensor, pc: PackedConv, y: torch.Tensor, *, dil: int = 1, pad: int = 0,
               lens_in: Optional[torch.Tensor] = None, lens_out: Optional[torch.Tensor] = None,
