@@ -638,7 +638,10 @@ int mi355_sine_source(const mi355_sine_source_args* a, void* stream);
 
 /* MLXSTFT.transform (istftnet.py:473-506) for small n_fft (<= 64): reflect-centred STFT with a
  * caller-supplied window, magnitude and atan2 phase, written channels-last:
- * x [B, L] -> y[b, f, 0:nb] = |X|, y[b, f, nb:2nb] = angle(X), f in [0, L/hop], nb = n_fft/2+1. */
+ * x [B, L] -> y[b, f, 0:nb] = |X|, y[b, f, nb:2nb] = angle(X), f in [0, L/hop], nb = n_fft/2+1.
+ * Precondition: L > n_fft/2 (checked) and, with lens, lens[b] > n_fft/2 for every item (NOT checked: lens lives on the device) -- the
+ * reflect padding is one reflection; below that the kernels clamp the index into the item and the values are not the reference's.
+ * Item b gets rows f in [0, lens[b]/hop]; rows past that are left untouched. */
 typedef struct {
   const float* x; int32_t ldx; int32_t L; const int32_t* lens; int32_t B;
   int32_t n_fft; int32_t hop; const float* window;

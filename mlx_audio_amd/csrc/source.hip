@@ -197,6 +197,7 @@ __global__ __launch_bounds__(256) void stft_magphase_kernel(const mi355_stft_mag
     int i = f * a.hop + n - N / 2;
     if (i < 0) i = -i;
     if (i >= len) i = 2 * (len - 1) - i;
+    i = i < 0 ? 0 : (i >= len ? len - 1 : i);   // as in the <20, 5> kernel: only reached where one reflection does not suffice (lens[b] <= n_fft / 2)
     xw[n] = (double)mul_rn(xb[i], win[n]);  // frames * w is an fp32 product in the reference
   }
   float* yr = a.y + (int64_t)b * a.y_bstride + (int64_t)f * a.ldy;
