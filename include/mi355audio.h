@@ -1227,6 +1227,62 @@ typedef struct {
 } mi355_dfn_apply_args;
 int mi355_dfn_apply(const mi355_dfn_apply_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mel-Band RoFormer (sts/models/mel_roformer): the ragged band split, the ragged band merge and the per-head sigmoid gate (bandsplit.hip).
+ * Three entry points added to ABI 37 (new structs and functions only).  Plain float32, no atomics, nothing allocated; every output element is
+ * a sum in a fixed order that does not depend on the launch geometry: two calls on the same bytes give the same bits.
+ *
+ * Spectra are the output of mi355_stft for the B * 2 channel items: item b, channel c, frame t, bin f at spec + (2 b + c) * spec_cstride +
+ * t * spec_tstride + 2 f (re, im).  A CaC index is j = 2 * bin + channel, 0 <= j < 2 F.  The band tables are CSR lists of CaC indices built on
+ * the host: band n owns band_idx[band_ptr[n] .. band_ptr[n + 1]) -- any indices in any order (no contiguity, no limit on how many bands share an
+ * index) -- and its vector u has bd_n = 2 * (band_ptr[n + 1] - band_ptr[n]) entries: u[2 m] = Re, u[2 m + 1] = Im of its m-th index.  A table
+ * index outside [0, 2 F) reads as zero.  No pointer needs more than float alignment.
+ * ------------------------------------------------------------------------------------------ */
+#define MI355_BAND_MAX_DIM 960    /* largest bd_n of mi355_band_split: 16 frames of a band stay in 60 KiB of LDS */
+/* BandSplit.split (mel_roformer/model.py:299-336) with the RMSNorm of model.py:26-42:
+ *   y[b, t, n, :] = W_n (u / max(||u||_2, 1e-12) * sqrt(bd_n) * gamma_n) + bias_n,   y [B, T, Nb, D] contiguous behind y_bstride.
+ * An all-zero frame gives exactly bias_n.  wt: the ragged concatenation of the TRANSPOSED weights, band n's [bd_n, D] block at wt + D * 2 *
+ * band_ptr[n]; gamma: ragged, band n at gamma + 2 * band_ptr[n]; bias [Nb, D].  One workgroup per (band, 16 frames, item): the normalised frames
+ * wait in LDS and each weight is read once per workgroup.  ||u||^2 is summed by one wave per frame (lane l adds entries l, l + 64, ... in order,
+ * then the xor butterfly); each output is a sequential sum over the band's entries.  max_band_dim: the largest bd_n of the table (the host
+ * built it), at most MI355_BAND_MAX_DIM, else MI355_ERR_UNSUPPORTED without a launch; a band wider than declared is left unwritten. */
+typedef struct {
+  const float* spec; int64_t spec_cstride; int64_t spec_tstride;
+  const int32_t* band_ptr; const int32_t* band_idx; int32_t n_idx;   /* [Nb + 1], [n_idx] (device); n_idx = band_ptr[Nb] */
+  int32_t max_band_dim;
+  const float* wt; const float* gamma; const float* bias;
+  int32_t B; int32_t T; int32_t F; int32_t Nb; int32_t D;
+  float* y; int64_t y_bstride;
+} mi355_band_split_args;
+int mi355_band_split(const mi355_band_split_args* a, void* stream);
+
+/* MaskEstimator's GLU, BandSplit.merge and the complex product (model.py:338-368,419-421,623-634) as one gather.  h [B, T, h_cols] (row t of
+ * item b at h + b * h_bstride + t * ldh) is the last per-band Linear's output, band n at columns [4 band_ptr[n], 4 band_ptr[n + 1]): bd_n values,
+ * then bd_n gates.  The host inverts the band tables: CaC index j lists its contributors inv_col / inv_bd [inv_ptr[j] .. inv_ptr[j + 1]) in
+ * ascending band order (the reference's addition order): col = the column of the contributor's real part (the imaginary part at col + 1), bd =
+ * that band's bd_n (the gates bd columns further).  A contributor whose columns leave [0, h_cols) is skipped.
+ *   mask[j] = (sum_c h[col_c + {0, 1}] * sigmoid(h[col_c + bd_c + {0, 1}])) / max(count_j, 1)   (complex; an index nobody covers has mask 0)
+ *   out[2 b + c, f, t] = spec[2 b + c, t, f] * mask[2 f + c]                                   (complex)
+ * at out + (2 b + c) * out_cstride + f * out_fstride + t * out_tstride (+ 0 / 1 for re / im; strides in floats): [B * 2, F, T] as
+ * mlx_audio.dsp.istft takes it, or any other order.  One thread per (item, frame, CaC index). */
+typedef struct {
+  const float* h; int64_t h_bstride; int64_t ldh; int32_t h_cols;
+  const int32_t* inv_ptr; const int32_t* inv_col; const int32_t* inv_bd; int32_t n_inv;   /* [2 F + 1], [n_inv], [n_inv] (device); n_inv = inv_ptr[2 F] */
+  const float* spec; int64_t spec_cstride; int64_t spec_tstride;
+  int32_t B; int32_t T; int32_t F;
+  float* out; int64_t out_cstride; int64_t out_fstride; int64_t out_tstride;
+} mi355_band_merge_args;
+int mi355_band_merge(const mi355_band_merge_args* a, void* stream);
+
+/* RoFormerAttention's gate (model.py:237-239), in place on channels-last views: x[b, l, h * dh + i] *= sigmoid(g[b, l, h]) for h < heads,
+ * i < dh; x [B, L, ldx >= heads * dh], g [B, L, ldg >= heads] (e.g. the columns behind q | k | v of one projection). */
+typedef struct {
+  float* x; int64_t x_bstride; int64_t ldx;
+  const float* g; int64_t g_bstride; int64_t ldg;
+  int32_t heads; int32_t dh; int32_t L; int32_t B;
+} mi355_head_gate_args;
+int mi355_head_gate(const mi355_head_gate_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -542,6 +542,127 @@ def dfn_apply(spec: torch.Tensor, m: torch.Tensor, erb_inv_fb: torch.Tensor, coe
     return torch.view_as_complex(out)
 
 
+# --------------------------------------------------------------------------------------- Mel-Band RoFormer band kernels
+BAND_MAX_DIM = 960   # MI355_BAND_MAX_DIM
+
+
+def band_inverse_host(band_ptr: np.ndarray, band_idx: np.ndarray, n_cac: int):
+    """The gather form of ``BandSplit.merge``: for every CaC index j < ``n_cac`` its contributors in ascending band order, as (inv_ptr [n_cac + 1],
+    inv_col, inv_bd) int32: ``inv_col`` = the column of the contributor's real part in the ragged row (band n starts at column 4 band_ptr[n]:
+    bd_n values, then bd_n gates), ``inv_bd`` = bd_n.  Indices outside [0, n_cac) contribute nowhere."""
+    band_ptr, band_idx = np.asarray(band_ptr, dtype=np.int64), np.asarray(band_idx, dtype=np.int64)
+    lists = [[] for _ in range(n_cac)]
+    for n in range(len(band_ptr) - 1):
+        p0, p1 = int(band_ptr[n]), int(band_ptr[n + 1])
+        for m in range(p1 - p0):
+            j = int(band_idx[p0 + m])
+            if 0 <= j < n_cac:
+                lists[j].append((4 * p0 + 2 * m, 2 * (p1 - p0)))
+    inv_ptr = np.zeros(n_cac + 1, dtype=np.int32)
+    inv_ptr[1:] = np.cumsum([len(c) for c in lists])
+    flat = [e for c in lists for e in c]
+    inv_col = np.array([e[0] for e in flat], dtype=np.int32)
+    inv_bd = np.array([e[1] for e in flat], dtype=np.int32)
+    return inv_ptr, inv_col, inv_bd
+
+
+@dataclass
+class BandTables:
+    """The CSR band tables of ``band_split`` / ``band_merge`` on the host (int32 numpy) and on the device."""
+    band_ptr: np.ndarray
+    band_idx: np.ndarray
+    freq_bins: int
+    ptr_d: torch.Tensor
+    idx_d: torch.Tensor
+    inv_ptr_d: torch.Tensor
+    inv_col_d: torch.Tensor
+    inv_bd_d: torch.Tensor
+    n_inv: int
+
+    @property
+    def num_bands(self) -> int:
+        return len(self.band_ptr) - 1
+
+    @property
+    def band_dims(self):
+        return [int(2 * (self.band_ptr[n + 1] - self.band_ptr[n])) for n in range(self.num_bands)]
+
+    @property
+    def h_cols(self) -> int:
+        return int(4 * self.band_ptr[-1])
+
+
+def band_tables(band_indices, freq_bins: int, device) -> BandTables:
+    """``band_indices``: one list of CaC indices (2 * bin + channel) per band, any order, any overlap."""
+    ptr = np.zeros(len(band_indices) + 1, dtype=np.int32)
+    ptr[1:] = np.cumsum([len(ix) for ix in band_indices])
+    idx = np.concatenate([np.asarray(ix, dtype=np.int32).reshape(-1) for ix in band_indices]).astype(np.int32) if ptr[-1] else np.zeros(0, np.int32)
+    inv_ptr, inv_col, inv_bd = band_inverse_host(ptr, idx, 2 * freq_bins)
+    up = lambda v: torch.from_numpy(np.ascontiguousarray(v if v.size else np.zeros(1, np.int32))).to(device)   # never a null pointer for an empty list
+    return BandTables(ptr, idx, freq_bins, up(ptr), up(idx), up(inv_ptr), up(inv_col), up(inv_bd), int(inv_ptr[-1]))
+
+
+def pack_band_split(weights, gammas, biases, device):
+    """Per-band ``Linear`` weights [D, bd_n], RMSNorm scales [bd_n] and biases [D] -> (wt, gamma, bias) of ``band_split``: the ragged concatenation
+    of the transposed weights, the ragged scales, bias [Nb, D]."""
+    f = lambda t: torch.as_tensor(t).detach().to(torch.float32).cpu()
+    wt = torch.cat([f(w).t().contiguous().reshape(-1) for w in weights])
+    return wt.to(device), torch.cat([f(g).reshape(-1) for g in gammas]).to(device), torch.stack([f(b) for b in biases]).contiguous().to(device)
+
+
+def _spec_planes(spec: torch.Tensor):
+    """complex64 [B2, T, F] (or float32 [B2, T, F, 2]) -> (float view, B2, T, F, channel stride, frame stride)."""
+    s = torch.view_as_real(spec) if spec.is_complex() else spec
+    assert s.dim() == 4 and s.shape[3] == 2 and s.dtype == torch.float32 and s.is_cuda and s.stride(3) == 1 and s.stride(2) == 2, (s.shape, s.stride(), s.dtype)
+    return s, s.shape[0], s.shape[1], s.shape[2], s.stride(0), s.stride(1)
+
+
+def band_split(spec: torch.Tensor, tab: BandTables, wt: torch.Tensor, gamma: torch.Tensor, bias: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The STFT of B * 2 channel items (``stft_frames``: complex64 [B * 2, T, F]) -> y [B, T, Nb, D] (``mi355_band_split``): per band the gather of
+    its CaC entries, ``x / max(||x||, 1e-12) * sqrt(bd) * gamma`` and the band's Linear, one launch."""
+    s, B2, T, F, cs, ts = _spec_planes(spec)
+    Nb, D = tab.num_bands, bias.shape[1]
+    assert B2 % 2 == 0 and F == tab.freq_bins and bias.shape == (Nb, D) and bias.is_contiguous() and wt.is_contiguous() and gamma.is_contiguous()
+    assert wt.numel() == D * 2 * int(tab.band_ptr[-1]) and gamma.numel() == 2 * int(tab.band_ptr[-1]) and wt.dtype == gamma.dtype == bias.dtype == torch.float32
+    if y is None:
+        y = torch.empty((B2 // 2, T, Nb, D), dtype=torch.float32, device=s.device)
+    assert y.shape == (B2 // 2, T, Nb, D) and y.dtype == torch.float32 and y[0].is_contiguous()
+    _lib.call_struct("mi355_band_split", "mi355_band_split_args", _stream(), spec=_ptr(s), spec_cstride=cs, spec_tstride=ts, band_ptr=_ptr(tab.ptr_d),
+                     band_idx=_ptr(tab.idx_d), n_idx=int(tab.band_ptr[-1]), max_band_dim=max(tab.band_dims), wt=_ptr(wt), gamma=_ptr(gamma), bias=_ptr(bias),
+                     B=B2 // 2, T=T, F=F, Nb=Nb, D=D, y=_ptr(y), y_bstride=y.stride(0))
+    return y
+
+
+def band_merge(h: torch.Tensor, tab: BandTables, spec: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """h [B, T, >= 4 * sum(index counts)] (the ragged output of the last per-band Linear: band n's bd_n values, then its bd_n gates, from column
+    4 band_ptr[n]) and the input spectrum -> the masked spectrum, complex64 [B * 2, F, T] (``mi355_band_merge``): GLU, the scatter as a gather in
+    ascending band order, the overlap average and the complex product.  ``out``: a float32 [B * 2, F, T, 2] view to fill (any f / t strides, e.g.
+    the transpose of a [B * 2, T, F, 2] buffer)."""
+    s, B2, T, F, cs, ts = _spec_planes(spec)
+    B, Th, _, hbs, ldh = _nlc(h)
+    assert 2 * B == B2 and Th == T and F == tab.freq_bins and h.shape[2] >= tab.h_cols
+    if out is None:
+        out = torch.empty((B2, F, T, 2), dtype=torch.float32, device=s.device)
+    assert out.shape == (B2, F, T, 2) and out.dtype == torch.float32 and out.stride(3) == 1
+    _lib.call_struct("mi355_band_merge", "mi355_band_merge_args", _stream(), h=_ptr(h), h_bstride=hbs, ldh=ldh, h_cols=tab.h_cols, inv_ptr=_ptr(tab.inv_ptr_d),
+                     inv_col=_ptr(tab.inv_col_d), inv_bd=_ptr(tab.inv_bd_d), n_inv=tab.n_inv,
+                     spec=_ptr(s), spec_cstride=cs, spec_tstride=ts, B=B, T=T, F=F, out=_ptr(out), out_cstride=out.stride(0), out_fstride=out.stride(1),
+                     out_tstride=out.stride(2))
+    return torch.view_as_complex(out)
+
+
+def head_gate(x: torch.Tensor, g: torch.Tensor, *, heads: int, dh: int) -> torch.Tensor:
+    """x[b, l, h * dh + i] *= sigmoid(g[b, l, h]) in place (``mi355_head_gate``); x [B, L, >= heads * dh] and g [B, L, >= heads] channels-last views."""
+    B, L, Cx, xbs, ldx = _nlc(x)
+    Bg, Lg, Cg, gbs, ldg = _nlc(g)
+    assert Bg == B and Lg == L
+    if Cx < heads * dh or Cg < heads:
+        raise _lib.Mi355Error(f"head_gate: {heads} heads of {dh} do not fit views of {Cx} and {Cg} columns")
+    _lib.call_struct("mi355_head_gate", "mi355_head_gate_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, g=_ptr(g), g_bstride=gbs, ldg=ldg,
+                     heads=heads, dh=dh, L=L, B=B)
+    return x
+
+
 # --------------------------------------------------------------------------------------- conv / linear
 def conv_gemm(x: torch.Tensor, pc: PackedConv, y: torch.Tensor, *, dil: int = 1, pad: int = 0,
               lens_in: Optional[torch.Tensor] = None, lens_out: Optional[torch.Tensor] = None,
