@@ -660,6 +660,25 @@ typedef struct {
 } mi355_istft_head_args;
 int mi355_istft_head(const mi355_istft_head_args* a, void* stream);
 
+/* The whole generator tail in ONE launch (new struct and function only; ABI stays 37): conv_post behind its LeakyReLU
+ * (istftnet.py:830-831, `x = leaky_relu(x); x = conv_post(x)`) plus the exp / sin / MLXSTFT.inverse of the generator's forward
+ * (istftnet.py:832-835, :508-541; dsp.istft dsp.py:436-513) -- i.e. mi355_conv_gemm(pre_act = LEAKY, K = 7, pad = 3, precision 2) followed by
+ * mi355_istft_head, without the [B, Fr, 2 nb] tensor between them.  x [B, L, Cin] float32 (rows 16-byte aligned), w / bias: the conv's
+ * packed bf16 image (mi355_pack_conv_weight_host; n-tile 0 is read, columns >= Cout are zero in it) and fp32 bias (nullable),
+ * audio [B, (L - 1) * hop].  Item b uses rows [0, lens[b]) (rows outside read as zero AFTER the LeakyReLU, as the conv's padding) and
+ * gets samples [0, (lens[b] - 1) * hop); samples beyond are left untouched.  The arithmetic per output value is that of the two launches
+ * (bf16 hi + lo passes, chunk -> tap order, bias, then the head's own steps); the path does not depend on B or on the number of blocks.
+ * Supported: Cin % 32 == 0, K == 7, dil == 1, pad == 3, n_fft == 20, hop == 5, Cout == 2 * (n_fft / 2 + 1) <= 32, pre_act == MI355_ACT_LEAKY,
+ * precision == 2; anything else returns MI355_ERR_UNSUPPORTED without a launch (the caller keeps the two launches). */
+typedef struct {
+  const float* x; int64_t x_bstride; int32_t ldx; int32_t Cin; int32_t L; const int32_t* lens; int32_t B;
+  const uint16_t* w; const float* bias; int32_t Cout; int32_t K; int32_t dil; int32_t pad;
+  int32_t pre_act; float pre_slope; int32_t precision;
+  int32_t n_fft; int32_t hop; const float* window;
+  float* audio; int32_t ld_audio;
+} mi355_conv_post_istft_args;
+int mi355_conv_post_istft(const mi355_conv_post_istft_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * mlx_audio.dsp (dsp.py): batched STFT / iSTFT for arbitrary n_fft (mixed-radix 2/3/4/5 +
  * generic-prime Stockham FFT staged in LDS) and the fused |X|^2 -> mel -> log front ends.

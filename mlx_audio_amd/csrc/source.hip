@@ -341,6 +341,66 @@ __global__ __launch_bounds__(256) void stft_magphase_fast_kernel(const mi355_stf
   }
 }
 
+// The per-frame arithmetic of the <N, HOP> iSTFT head, stated ONCE for the two kernels that run it (istft_head_fast_kernel on a stored conv_post
+// output, conv_post_istft_kernel on the conv_post values it has just computed): spectrum, inverse transform + window, overlap-add + trim.
+//
+// head_frame_spectrum: one frame's 2 nb conv_post values (xr, LDS) -> mag = exp(x[:nb]), phase = sin(x[nb:]), spec = mag (cos phase + i sin phase);
+// a frame outside [0, Fr) contributes zeros.
+template <int N>
+__device__ __forceinline__ void head_frame_spectrum(const float* xr, const bool valid, double (&re)[N / 2 + 1], double (&im)[N / 2 + 1]) {
+  constexpr int nb = N / 2 + 1;
+#pragma unroll
+  for (int k = 0; k < nb; ++k) {
+    const float mag = expf(xr[k]);
+    const float ph = sinf(xr[nb + k]);
+    float sn, cs;
+    sincosf(ph, &sn, &cs);   // one argument reduction for both (|ph| <= 1); same values as sinf / cosf
+    re[k] = valid ? (double)mul_rn(mag, cs) : 0.0;
+    im[k] = valid ? (double)mul_rn(mag, sn) : 0.0;
+  }
+}
+// head_frame_synth: irfft(N) of the frame's spectrum (fp64 sums, rounded once) times the synthesis window -> tr[0..N) (LDS)
+template <int N>
+__device__ __forceinline__ void head_frame_synth(const double (&re)[N / 2 + 1], const double (&im)[N / 2 + 1], const float* window, const SmallTw& tw, float* tr) {
+  constexpr int nb = N / 2 + 1;
+#pragma unroll
+  for (int n = 0; n <= N / 2; ++n) {
+    const double base = (n & 1) ? re[0] - re[nb - 1] : re[0] + re[nb - 1];
+    double A = 0.0, Bs = 0.0;
+#pragma unroll
+    for (int k = 1; k < nb - 1; ++k) {
+      const int m = (k * n) % N;
+      A = fma(re[k], tw.c[m], A);
+      Bs = fma(im[k], tw.s[m], Bs);
+    }
+    constexpr double inv_n = 1.0 / (double)N;   // (a multiply instead of 20 fp64 divisions per frame; the fp32 rounding below hides the last bit)
+    tr[n] = mul_rn((float)((base + 2.0 * (A - Bs)) * inv_n), window[n]);
+    if (n > 0 && n < N / 2) tr[N - n] = mul_rn((float)((base + 2.0 * (A + Bs)) * inv_n), window[N - n]);
+  }
+}
+// head_overlap_add: the FO * HOP untrimmed positions workgroup `blk` owns, each the sum of the <= ceil(N / HOP) windowed frames over it (a gather out of
+// td, whose row 0 is frame fa), divided by the window envelope, trimmed by N / 2 on each side.  Samples at and beyond (Fr - 1) * HOP stay unwritten.
+template <int N, int HOP, int FO, int TS>
+__device__ __forceinline__ void head_overlap_add(const float* td, const int fa, const int Fr, const int blk, const float* window, float* audio_b, const int tid) {
+  const int total = (Fr - 1) * HOP;  // trimmed length
+  for (int i = tid; i < FO * HOP; i += 256) {
+    const int p = blk * FO * HOP + i;  // untrimmed position
+    const int t = p - N / 2;
+    if (t < 0 || t >= total) continue;
+    int f_lo = (p - N + HOP) / HOP; if (p - N + 1 <= 0) f_lo = 0;
+    int f_hi = p / HOP; if (f_hi > Fr - 1) f_hi = Fr - 1;
+    float rec = 0.f, ws = 0.f;
+    for (int f = f_lo; f <= f_hi; ++f) {
+      const int n = p - f * HOP;
+      if (n < 0 || n >= N) continue;
+      rec = add_rn(rec, td[(f - fa) * TS + n]);
+      const float w = window[n];
+      ws = add_rn(ws, mul_rn(w, w));
+    }
+    audio_b[t] = (ws > 1e-10f) ? rec / ws : rec;
+  }
+}
+
 template <int N, int HOP>
 __global__ __launch_bounds__(256) void istft_head_fast_kernel(const mi355_istft_head_args a, const SmallTw tw) {
   constexpr int nb = N / 2 + 1, HALO = (N + HOP - 1) / HOP, FT = 256, FO = FT - HALO, XS = 2 * nb + 1, TS = N + 1;
@@ -357,52 +417,164 @@ __global__ __launch_bounds__(256) void istft_head_fast_kernel(const mi355_istft_
   __syncthreads();
   {
     const int f = fa + tid;
-    const bool valid = f >= 0 && f < Fr;
-    const float* xr = xin + tid * XS;
     double re[nb], im[nb];
-#pragma unroll
-    for (int k = 0; k < nb; ++k) {
-      const float mag = expf(xr[k]);
-      const float ph = sinf(xr[nb + k]);
-      float sn, cs;
-      sincosf(ph, &sn, &cs);   // one argument reduction for both (|ph| <= 1); same values as sinf / cosf
-      re[k] = valid ? (double)mul_rn(mag, cs) : 0.0;
-      im[k] = valid ? (double)mul_rn(mag, sn) : 0.0;
-    }
-    float* tr = td + tid * TS;
-#pragma unroll
-    for (int n = 0; n <= N / 2; ++n) {
-      const double base = (n & 1) ? re[0] - re[nb - 1] : re[0] + re[nb - 1];
-      double A = 0.0, Bs = 0.0;
-#pragma unroll
-      for (int k = 1; k < nb - 1; ++k) {
-        const int m = (k * n) % N;
-        A = fma(re[k], tw.c[m], A);
-        Bs = fma(im[k], tw.s[m], Bs);
-      }
-      constexpr double inv_n = 1.0 / (double)N;   // (a multiply instead of 20 fp64 divisions per frame; the fp32 rounding below hides the last bit)
-      tr[n] = mul_rn((float)((base + 2.0 * (A - Bs)) * inv_n), a.window[n]);
-      if (n > 0 && n < N / 2) tr[N - n] = mul_rn((float)((base + 2.0 * (A + Bs)) * inv_n), a.window[N - n]);
-    }
+    head_frame_spectrum<N>(xin + tid * XS, f >= 0 && f < Fr, re, im);
+    head_frame_synth<N>(re, im, a.window, tw, td + tid * TS);
   }
   __syncthreads();
-  const int total = (Fr - 1) * HOP;  // trimmed length
-  for (int i = tid; i < FO * HOP; i += 256) {
-    const int p = blockIdx.x * FO * HOP + i;  // untrimmed position
-    const int t = p - N / 2;
-    if (t < 0 || t >= total) continue;
-    int f_lo = (p - N + HOP) / HOP; if (p - N + 1 <= 0) f_lo = 0;
-    int f_hi = p / HOP; if (f_hi > Fr - 1) f_hi = Fr - 1;
-    float rec = 0.f, ws = 0.f;
-    for (int f = f_lo; f <= f_hi; ++f) {
-      const int n = p - f * HOP;
-      if (n < 0 || n >= N) continue;
-      rec = add_rn(rec, td[(f - fa) * TS + n]);
-      const float w = a.window[n];
-      ws = add_rn(ws, mul_rn(w, w));
+  head_overlap_add<N, HOP, FO, TS>(td, fa, Fr, blockIdx.x, a.window, a.audio + (int64_t)b * a.ld_audio, tid);
+}
+
+// ---------------------------------------------------------------- conv_post + iSTFT head in one launch
+// The generator's tail (istftnet.py:830-835): conv_post (C_in -> 2 nb channels, 7 taps, behind a LeakyReLU) and the head above, without the
+// [B, Fr, 2 nb] tensor between them.  As two launches the conv ran its 22 columns on a 64-column tile (2.9x the matrix work of one 32-column
+// fragment) and the 195 MB of `post` (64 utterances) were written once and read once.  Here a workgroup takes the head's block of frames
+// (256 staged, 252 owned) and, per 32-channel chunk:
+//   window   all four waves stream the chunk's fp32 rows (the block's 256 frames + 3 halo rows on each side) into registers one chunk ahead,
+//            apply LeakyReLU, zero the rows outside [0, lens[b]) AFTER it, split into bf16 hi + lo and write conv_ws4's LDS image (64-byte rows,
+//            16-byte pieces XOR-swizzled by (row >> 2) & 3); the chunk's 14 weight fragments of n-tile 0 (14 KB of the conv's own packed image)
+//            are staged beside it;
+//   conv     wave w owns frames [64 w, +64) = two 32x32 accumulators; per tap and 16-channel half: hi MFMA, then lo MFMA into the same
+//            accumulator -- chunk -> tap -> half -> hi, lo: per accumulator element the order of conv_ws4_kernel<2, ...> (the benchmark batch's
+//            waveforms are bit-equal to the two launches'; small launches, which the dispatcher gives to other conv kernels, differ in the last bits).
+// The accumulators + bias go to LDS (columns >= 22 are dropped), and the head's three steps run on them as in istft_head_fast_kernel.
+// The global loads of chunk c + 1 are in flight under the MFMAs of chunk c; the barriers wait for LDS only.
+constexpr int kCpTaps = 7;
+
+__device__ __forceinline__ void lds_only_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS reads / writes are done (global loads stay in flight)
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+template <int N, int HOP>
+__global__ __launch_bounds__(256) void conv_post_istft_kernel(const mi355_conv_post_istft_args a, const SmallTw tw) {
+  constexpr int nb = N / 2 + 1, HALO = (N + HOP - 1) / HOP, FT = 256, FO = FT - HALO, XS = 2 * nb + 1, TS = N + 1;
+  constexpr int K = kCpTaps, PAD = (K - 1) / 2, R = FT + K - 1, NP = (R + 31) / 32, IMG = R * 64;   // window rows, passes of 32 rows, bytes of one 16-bit image
+  constexpr int WB = K * 2048, WPIECES = WB / 16, NWR = (WPIECES + 255) / 256;                      // the chunk's weight fragments: K taps x 2 halves x 1 KB
+  constexpr int XIN_BYTES = FT * XS * 4, TD_BYTES = FT * TS * 4;
+  static_assert(2 * nb <= 32, "one 32-column fragment");
+  static_assert(XIN_BYTES % 16 == 0 && XIN_BYTES + TD_BYTES <= 2 * IMG + WB, "the head's arrays reuse the window");
+  __shared__ __attribute__((aligned(16))) char smem[2 * IMG + WB];
+  char* const A_hi = smem;
+  char* const A_lo = smem + IMG;
+  char* const W_l = smem + 2 * IMG;
+  float* const xin = (float*)smem;                 // [FT][XS]  (after the last MFMA)
+  float* const td = (float*)(smem + XIN_BYTES);    // [FT][TS]
+
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int Fr = a.lens ? min(a.lens[b], a.L) : a.L;
+  if (Fr < 2 || (int)blockIdx.x * FO > Fr) return;   // no sample of this block lies inside the item (workgroup-uniform, ahead of every barrier)
+  const int fa = blockIdx.x * FO - HALO;             // first staged frame (may be negative)
+  const int g0 = fa - PAD;                           // input row of window row 0
+  const int nch = a.Cin >> 5;
+  const int c4 = (tid & 7) * 4, prow = tid >> 3;
+  const float* xb = a.x + (int64_t)b * a.x_bstride;
+  const int64_t wstep = (int64_t)(((a.Cout + 127) >> 7) << 2) * 2048;   // bytes between slices (chunk, tap) of the packed image; n-tile 0 leads each
+  const float slope = a.pre_slope;
+
+  float4 st[NP];
+  static_assert(NWR == 4 && WPIECES > 3 * 256, "weight staging: three full passes of 256 pieces and a partial one");
+  uint4 wr0, wr1, wr2, wr3;   // (named, not an array: hipcc kept a uint4[4] in scratch)
+  const bool wlast = tid + 3 * 256 < WPIECES;
+  auto load_chunk = [&](const int chunk) {
+    // piece p of the chunk's weights = 16 bytes at slice (chunk, tap p >> 7), offset (p & 127) * 16 of n-tile 0; the lanes without a piece in the
+    // last pass repeat an earlier one and do not write it
+    auto wsrc = [&](const int p) { return (const uint4*)((const char*)a.w + (int64_t)(chunk * K + (p >> 7)) * wstep + (p & 127) * 16); };
+    wr0 = *wsrc(tid);
+    wr1 = *wsrc(tid + 256);
+    wr2 = *wsrc(tid + 512);
+    wr3 = *wsrc(wlast ? tid + 768 : tid);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      int g = g0 + prow + 32 * i;
+      g = g < 0 ? 0 : (g >= a.L ? a.L - 1 : g);   // rows outside the item are masked in stage_chunk; the address stays inside the tensor
+      st[i] = *(const float4*)(xb + (int64_t)g * a.ldx + chunk * 32 + c4);
     }
-    a.audio[(int64_t)b * a.ld_audio + t] = (ws > 1e-10f) ? rec / ws : rec;
+  };
+  auto stage_chunk = [&]() {
+    *(uint4*)(W_l + tid * 16) = wr0;
+    *(uint4*)(W_l + (tid + 256) * 16) = wr1;
+    *(uint4*)(W_l + (tid + 512) * 16) = wr2;
+    if (wlast) *(uint4*)(W_l + (tid + 768) * 16) = wr3;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int r = prow + 32 * i;
+      if (r >= R) continue;
+      const int g = g0 + r;
+      const bool rowok = g >= 0 && g < Fr;
+      const float v[4] = {st[i].x, st[i].y, st[i].z, st[i].w};
+      float tt[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float m = mul_rn(v[j], slope);
+        const float u = v[j] > 0.f ? v[j] : m;
+        tt[j] = rowok ? u : 0.f;
+      }
+      uint2 ph, pl;
+      ph.x = pack_bf16x2(tt[0], tt[1]);
+      ph.y = pack_bf16x2(tt[2], tt[3]);
+      const float h0 = __builtin_bit_cast(float, ph.x << 16), h1 = __builtin_bit_cast(float, ph.x & 0xffff0000u);
+      const float h2 = __builtin_bit_cast(float, ph.y << 16), h3 = __builtin_bit_cast(float, ph.y & 0xffff0000u);
+      pl.x = pack_bf16x2(sub_rn(tt[0], h0), sub_rn(tt[1], h1));
+      pl.y = pack_bf16x2(sub_rn(tt[2], h2), sub_rn(tt[3], h3));
+      const int addr = r * 64 + ((((c4 >> 3) ^ ((r >> 2) & 3))) << 4) + ((c4 & 4) << 1);
+      *(uint2*)(A_hi + addr) = ph;
+      *(uint2*)(A_lo + addr) = pl;
+    }
+  };
+
+  f32x16 acc[2];
+#pragma unroll
+  for (int mf = 0; mf < 2; ++mf)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[mf][r] = 0.f;
+  const int hl = lane & 31, hh = lane >> 5;
+
+  load_chunk(0);
+  for (int chunk = 0; chunk < nch; ++chunk) {
+    if (chunk > 0) lds_only_barrier();   // every wave is done with the previous chunk's window and weights
+    stage_chunk();
+    if (chunk + 1 < nch) load_chunk(chunk + 1);
+    lds_only_barrier();
+#pragma unroll
+    for (int tap = 0; tap < K; ++tap) {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 bf = *(const bf16x8*)(W_l + tap * 2048 + kk * 1024 + lane * 16);
+#pragma unroll
+        for (int mf = 0; mf < 2; ++mf) {
+          const int row = wave * 64 + mf * 32 + hl + tap;
+          const int addr = row * 64 + (((kk * 2 + hh) ^ ((row >> 2) & 3)) << 4);
+          const bf16x8 h = *(const bf16x8*)(A_hi + addr);
+          const bf16x8 l = *(const bf16x8*)(A_lo + addr);
+          acc[mf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h, bf, acc[mf], 0, 0, 0);
+          acc[mf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(l, bf, acc[mf], 0, 0, 0);
+        }
+      }
+    }
   }
+  lds_only_barrier();   // the window is free: the 2 nb columns of every frame take its place
+  if (hl < 2 * nb) {    // accumulator register r of lane (hl, hh): frame 64 wave + 32 mf + (r & 3) + 8 (r >> 2) + 4 hh, column hl
+    const float bias = a.bias ? a.bias[hl] : 0.f;
+#pragma unroll
+    for (int mf = 0; mf < 2; ++mf)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = wave * 64 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        xin[j * XS + hl] = add_rn(acc[mf][r], bias);
+      }
+  }
+  __syncthreads();
+  {
+    const int f = fa + tid;
+    double re[nb], im[nb];
+    head_frame_spectrum<N>(xin + tid * XS, f >= 0 && f < Fr, re, im);
+    head_frame_synth<N>(re, im, a.window, tw, td + tid * TS);
+  }
+  __syncthreads();
+  head_overlap_add<N, HOP, FO, TS>(td, fa, Fr, blockIdx.x, a.window, a.audio + (int64_t)b * a.ld_audio, tid);
 }
 
 SmallTw make_small_tw(int N) {
@@ -640,6 +812,27 @@ extern "C" int mi355_istft_head(const mi355_istft_head_args* ap, void* stream) {
   MI355_CLEAR_ERROR();
   hipLaunchKernelGGL(istft_head_kernel, dim3(blocks, a.B), dim3(256), lds, (hipStream_t)stream, a);
   MI355_LAUNCH_CHECK("istft_head");
+  return MI355_OK;
+}
+
+extern "C" int mi355_conv_post_istft(const mi355_conv_post_istft_args* ap, void* stream) {
+  MI355_REQUIRE(ap && ap->x && ap->w && ap->window && ap->audio, "conv_post_istft: null tensor");
+  const mi355_conv_post_istft_args a = *ap;
+  if (!(a.Cin > 0 && a.Cin % 32 == 0 && a.K == kCpTaps && a.dil == 1 && a.pad == (kCpTaps - 1) / 2 && a.n_fft == 20 && a.hop == 5 &&
+        a.Cout == 2 * (a.n_fft / 2 + 1) && a.Cout <= 32 && a.pre_act == MI355_ACT_LEAKY && a.precision == 2)) {
+    mi355_set_error("conv_post_istft: unsupported shape (Cin=%d K=%d dil=%d pad=%d Cout=%d n_fft=%d hop=%d pre_act=%d precision=%d)", a.Cin, a.K, a.dil,
+                    a.pad, a.Cout, a.n_fft, a.hop, a.pre_act, a.precision);
+    return MI355_ERR_UNSUPPORTED;
+  }
+  MI355_REQUIRE(a.B > 0 && a.B <= 65535 && a.L > 1 && a.ldx >= a.Cin && (a.B == 1 || a.x_bstride >= (int64_t)a.L * a.ldx), "conv_post_istft: bad shape");
+  MI355_REQUIRE((a.ldx & 3) == 0 && (a.x_bstride & 3) == 0 && (((uintptr_t)a.x | (uintptr_t)a.w) & 15) == 0, "conv_post_istft: rows must be 16-byte aligned");
+  MI355_REQUIRE(a.B == 1 || a.ld_audio >= (a.L - 1) * a.hop, "conv_post_istft: audio rows shorter than (L - 1) * hop");
+  static const SmallTw tw20 = make_small_tw(20);
+  constexpr int FO = 256 - (20 + 5 - 1) / 5;
+  const int total_untrimmed = (a.L - 1) * 5 + 20;
+  MI355_CLEAR_ERROR();
+  hipLaunchKernelGGL((conv_post_istft_kernel<20, 5>), dim3((total_untrimmed + FO * 5 - 1) / (FO * 5), a.B), dim3(256), 0, (hipStream_t)stream, a, tw20);
+  MI355_LAUNCH_CHECK("conv_post_istft");
   return MI355_OK;
 }
 

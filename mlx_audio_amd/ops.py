@@ -1588,6 +1588,38 @@ def istft_head(x: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, audi
     return audio
 
 
+def conv_post_istft_eligible(pc: PackedConv, n_fft: int, hop: int, *, dil: int = 1, pad: int = 3, pre_act: int = ACT_LEAKY, precision: int = 2,
+                             pre_fq=None) -> bool:
+    """Shapes ``mi355_conv_post_istft`` takes (the header's list).  Nothing here looks at the batch or at the number of frames: an utterance takes the
+    same path alone and inside a batch."""
+    return (pc.cin % 32 == 0 and pc.k == 7 and dil == 1 and pad == 3 and n_fft == 20 and hop == 5 and pc.cout == n_fft + 2 and pc.cout <= 32
+            and pre_act == ACT_LEAKY and precision == 2 and not pc.f16 and not pc.mx and pre_fq is None)
+
+
+def conv_post_istft(x: torch.Tensor, pc: PackedConv, n_fft: int, hop: int, window: torch.Tensor, audio: torch.Tensor, *, lens=None,
+                    dil: int = 1, pad: int = 3, pre_act: int = ACT_LEAKY, pre_slope: float = 0.01, precision: int = 2, pre_fq=None):
+    """The generator tail: ``audio = istft_head(conv_post(act(x)))``, x [B, L, Cin] -> audio [B, (L - 1) * hop].  One launch
+    (``mi355_conv_post_istft``) where ``conv_post_istft_eligible``; every other call runs ``conv_gemm`` into a scratch ``post`` tensor and
+    ``istft_head`` on it, the two launches the fused kernel stands for."""
+    B, L, _, xbs, ldx = _nlc(x)
+    if conv_post_istft_eligible(pc, n_fft, hop, dil=dil, pad=pad, pre_act=pre_act, precision=precision, pre_fq=pre_fq):
+        assert audio.dim() == 2 and audio.stride(1) == 1 and audio.dtype == torch.float32 and audio.shape[1] >= (L - 1) * hop
+        if PROFILE is not None:   # the conv's entry of the per-launch table (conv_gemm above); the interval also holds the head's work
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            PROFILE.append(((L * B) if lens is None else lens.sum(), pc.cin, pc.cout, pc.k, dil, 0, e0, e1))
+        _lib.call_struct("mi355_conv_post_istft", "mi355_conv_post_istft_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, Cin=pc.cin, L=L,
+                         lens=_ptr(lens), B=B, w=_ptr(pc.w), bias=_ptr(pc.bias), Cout=pc.cout, K=pc.k, dil=dil, pad=pad, pre_act=pre_act,
+                         pre_slope=pre_slope, precision=precision, n_fft=n_fft, hop=hop, window=_ptr(window), audio=_ptr(audio),
+                         ld_audio=audio.stride(0))
+        if PROFILE is not None:
+            e1.record()
+        return audio
+    post = torch.empty((B, L, round_up(pc.cout, 4)), dtype=torch.float32, device=x.device)[:, :, :pc.cout]
+    conv_gemm(x, pc, post, dil=dil, pad=pad, lens_in=lens, lens_out=lens, pre_act=pre_act, pre_slope=pre_slope, precision=precision, pre_fq=pre_fq)
+    return istft_head(post, n_fft, hop, window, audio, lens=lens)
+
+
 # --------------------------------------------------------------------------------------- generic dsp
 def stft_frames(x: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, pad_mode: int, n_frames: int):
     """x [B, L] -> complex64 [B, n_frames, n_fft//2+1]."""

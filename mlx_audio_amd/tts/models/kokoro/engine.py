@@ -835,10 +835,16 @@ class KokoroEngine:
             x, L, lens_x = acc, Lo, lens_o
             if return_intermediates:
                 trace[f"stage{i}"] = acc.clone()
-        post = self._new(B, L, round_up(nb2, 4))
-        self._convq(f"{g_n}.conv_post", x, self.conv_post, post[:, :, :nb2], pad=3, lens_in=lens_x, lens_out=lens_x, pre_act=ACT_LEAKY, pre_slope=0.01)
         audio = self._new(B, (L - 1) * self.hop, zero=True)
-        ops.istft_head(post[:, :, :nb2], self.n_fft, self.hop, self.window, audio, lens=lens_x)
+        # conv_post and the iSTFT head: one launch and no `post` tensor where the weight image and n_fft / hop are the fused kernel's (never a matter
+        # of B or L; ops.conv_post_istft runs the two launches otherwise) -- unless the trace wants `post` or conv_post quantises its input (KittenTTS)
+        post = None
+        if not return_intermediates and not (self.qmods and self._isq(f"{g_n}.conv_post")):
+            ops.conv_post_istft(x, self.conv_post, self.n_fft, self.hop, self.window, audio, lens=lens_x, pre_slope=0.01, precision=self._prec(self.conv_post))
+        else:
+            post = self._new(B, L, round_up(nb2, 4))
+            self._convq(f"{g_n}.conv_post", x, self.conv_post, post[:, :, :nb2], pad=3, lens_in=lens_x, lens_out=lens_x, pre_act=ACT_LEAKY, pre_slope=0.01)
+            ops.istft_head(post[:, :, :nb2], self.n_fft, self.hop, self.window, audio, lens=lens_x)
         outs = [audio[b, : Fs[b] * 2 * up] for b in range(B)]
         durs = [dur[b, : Ts[b]] for b in range(B)]
         if return_intermediates:
