@@ -1302,6 +1302,65 @@ typedef struct {
 } mi355_head_gate_args;
 int mi355_head_gate(const mi355_head_gate_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SenseVoice-Small (stt/models/sensevoice/sensevoice.py): the encoder's input assembly and the CTC head behind the ctc_lo GEMM (sanm.hip).
+ * Three entry points added to ABI 37 (new structs and functions only; no existing layout changed).  Plain float32, no atomics, nothing
+ * allocated; every output is computed in a fixed order that does not depend on the launch geometry: two calls on the same bytes give the
+ * same bits.  (The SAN-M memory term itself is mi355_fsmn_memory.)
+ * ------------------------------------------------------------------------------------------ */
+/* _apply_lfr + _apply_cmvn (sensevoice.py:47-80), the query rows of SenseVoiceSmall.__call__ (:426-433) and the encoder's scale and
+ * SinusoidalPositionEncoder (:106-122,322-324) in one launch.  With W = lfr_m * D, left = (lfr_m - 1) / 2, n_b = lens[b] (NULL: T) and
+ * R_b = 4 + ceil(n_b / lfr_n), the output x [B, 4 + ceil(T / lfr_n), W] is
+ *   row r < 4:           u = embed[qids[b, r]]
+ *   row 4 + i < R_b:     u[j * D + d] = feats[b, clamp(i * lfr_n + j - left, 0, n_b - 1), d]   (j < lfr_m: left-padded with frame 0, right-padded
+ *                        with the ITEM's last valid frame, not with row T - 1 of the batch), then u = (u + means) * istd when means / istd are given
+ *   every row r < R_b:   x[b, r] = u * scale + pe[r]     (each operation rounded on its own, in this order; pe NULL: no position term)
+ *   rows r >= R_b:       zeros
+ * and out_lens[b] = R_b.  pe [pe_rows >= 4 + ceil(T / lfr_n), W] is the host's sinusoidal table (positions from 1, sines in the first half of
+ * the columns, cosines in the second).  qids in [0, 16).  1 <= lens[b] <= T is the caller's contract (an item without a frame has no last
+ * frame to pad with); the kernel clamps what it reads so that no index leaves feats.  lfr_m = lfr_n = 1 passes already stacked features. */
+typedef struct {
+  const float* feats; int64_t feats_bstride; int32_t ldf;  /* [B, T, ldf], ldf >= D */
+  const int32_t* lens;                                     /* [B] nullable => T */
+  const float* means; const float* istd;                   /* [W] nullable (together) */
+  const float* embed; const int32_t* qids;                 /* [16, W]; [B, 4] */
+  const float* pe; int32_t pe_rows;                        /* [pe_rows, W] nullable */
+  int32_t lfr_m; int32_t lfr_n; float scale;
+  int32_t B; int32_t T; int32_t D;
+  float* x; int64_t x_bstride; int32_t ldx;                /* [B, 4 + ceil(T / lfr_n), ldx], ldx >= W */
+  int32_t* out_lens;                                       /* [B] */
+} mi355_sanm_input_args;
+int mi355_sanm_input(const mi355_sanm_input_args* a, void* stream);
+
+/* nn.log_softmax + mx.argmax over the vocabulary (sensevoice.py:437,451,468-493), one read of each row with an online maximum / sum of
+ * exponentials.  Per row of logits [rows, ld >= V], any V >= 1:
+ *   ids = the arg-max (the first maximum on ties, as mx.argmax);
+ *   gap = max - the largest value at any OTHER index (0 on a tie, 0 for V = 1);
+ *   lp  = the arg-max's log-probability, max - logsumexp = -log(sum_c exp(x_c - max));
+ *   logp (nullable) [rows, ld_logp >= V] = (x_c - max) - log(sum_c exp(x_c - max)): a second pass over the row just read; logp may BE logits
+ *   (in place, ld_logp == ld).
+ * Finite logits are the caller's contract.  One workgroup per row: thread t sums the columns t, t + 256, ... in ascending order, the 256
+ * partial sums are rescaled to the row maximum and joined by the wave butterfly and (w0 + w1) + (w2 + w3). */
+typedef struct {
+  const float* logits; int64_t ld; int64_t rows; int32_t V;
+  int32_t* ids; float* gap; float* lp;                     /* [rows] each */
+  float* logp; int64_t ld_logp;                            /* nullable */
+} mi355_ctc_rows_args;
+int mi355_ctc_rows(const mi355_ctc_rows_args* a, void* stream);
+
+/* The collapse of _greedy_ctc_decode (sensevoice.py:450-463) on the rows skip .. lens[b] - 1 of ids [B, T] (row stride ld_ids >= T): drop
+ * every row whose id equals the id of the row before it, then drop the blanks -- so a, blank, a keeps both a.  Row `skip` has no row before
+ * it (the reference decodes log_probs[4:] on its own: an id equal to row skip - 1's still counts).  tokens [B, T] receives the kept ids in
+ * order, counts [B] their number, frames [B, T] (nullable) the row index of each kept id (the first row of its run); the slots at and
+ * beyond counts[b] hold -1.  lens NULL => T; lens[b] <= skip gives counts[b] = 0. */
+typedef struct {
+  const int32_t* ids; int64_t ld_ids;
+  const int32_t* lens; int32_t skip; int32_t blank;
+  int32_t B; int32_t T;
+  int32_t* tokens; int32_t* counts; int32_t* frames;       /* [B, T] contiguous; [B]; [B, T] nullable */
+} mi355_ctc_collapse_args;
+int mi355_ctc_collapse(const mi355_ctc_collapse_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

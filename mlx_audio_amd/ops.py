@@ -1450,6 +1450,74 @@ def stencil2d_k3s2(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor
     return y
 
 
+def sanm_rows(T: int, lfr_n: int) -> int:
+    """Rows of ``sanm_input``'s output for ``T`` frames: the four query rows and ``ceil(T / lfr_n)`` stacked frames."""
+    return 4 + (T + lfr_n - 1) // lfr_n
+
+
+def sanm_input(feats: torch.Tensor, embed: torch.Tensor, qids: torch.Tensor, pe: Optional[torch.Tensor], *, lfr_m: int, lfr_n: int, scale: float,
+               lens: Optional[torch.Tensor] = None, means: Optional[torch.Tensor] = None, istd: Optional[torch.Tensor] = None,
+               x: Optional[torch.Tensor] = None):
+    """SenseVoice's encoder input in one launch (``mi355_sanm_input``): ``feats`` [B, T, D] (the fbank; ``lens`` int32 [B], every one in [1, T]) ->
+    ``(x [B, 4 + ceil(T / lfr_n), lfr_m * D], out_lens int32 [B])``.  Rows 0..3 are ``embed[qids[b]]`` (``embed`` [16, W], ``qids`` int32 [B, 4]), row
+    ``4 + i`` the low-frame-rate stack of ``lfr_m`` frames at hop ``lfr_n`` (edge frames repeated, the right edge being the item's own last frame) after
+    ``(. + means) * istd``; every valid row is ``row * scale + pe[row]`` (``pe`` [>= rows, W] or None) and the rows at and beyond ``out_lens[b]`` are zero."""
+    B, T, D, fbs, ldf = _nlc(feats)
+    W, rows = lfr_m * D, sanm_rows(T, lfr_n)
+    f32 = lambda t, n: t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == n
+    assert f32(embed, 16 * W) and qids.dtype == torch.int32 and qids.is_cuda and qids.is_contiguous() and tuple(qids.shape) == (B, 4)
+    assert (means is None) == (istd is None) and (means is None or (f32(means, W) and f32(istd, W)))
+    if pe is not None:
+        assert pe.dim() == 2 and pe.shape[1] == W and pe.is_contiguous() and pe.dtype == torch.float32 and pe.is_cuda
+        if pe.shape[0] < rows:
+            raise _lib.Mi355Error(f"sanm_input: the position table holds {pe.shape[0]} rows, the batch needs {rows}")
+    if x is None:
+        x = torch.empty((B, rows, W), dtype=torch.float32, device=feats.device)
+    Bx, Rx, Wx, xbs, ldx = _nlc(x)
+    assert (Bx, Rx, Wx) == (B, rows, W)
+    out_lens = torch.empty((B,), dtype=torch.int32, device=feats.device)
+    _lib.call_struct("mi355_sanm_input", "mi355_sanm_input_args", _stream(), feats=_ptr(feats), feats_bstride=fbs, ldf=ldf, lens=_lens_arg(lens, B),
+                     means=_ptr(means), istd=_ptr(istd), embed=_ptr(embed), qids=_ptr(qids), pe=_ptr(pe), pe_rows=0 if pe is None else pe.shape[0],
+                     lfr_m=lfr_m, lfr_n=lfr_n, scale=scale, B=B, T=T, D=D, x=_ptr(x), x_bstride=xbs, ldx=ldx, out_lens=_ptr(out_lens))
+    return x, out_lens
+
+
+def ctc_rows(logits: torch.Tensor, *, ids: Optional[torch.Tensor] = None, gap: Optional[torch.Tensor] = None, lp: Optional[torch.Tensor] = None,
+             logp: Optional[torch.Tensor] = None):
+    """Per row of ``logits`` [rows, V] (row stride >= V), one read (``mi355_ctc_rows``): ``(ids int32, gap, lp)`` [rows] each -- the arg-max (first
+    maximum on ties), the distance to the largest value at any other index, and the arg-max's log-probability.  ``ids`` / ``gap`` / ``lp``: contiguous
+    [rows] outputs to fill (slices of a caller's buffers: the head runs in row chunks); ``logp`` [rows, V] also receives ``logits - logsumexp`` and may be
+    ``logits`` itself."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.float32 and logits.is_cuda
+    rows, V = logits.shape
+    dev = logits.device
+    ids = torch.empty((rows,), dtype=torch.int32, device=dev) if ids is None else ids
+    gap = torch.empty((rows,), dtype=torch.float32, device=dev) if gap is None else gap
+    lp = torch.empty((rows,), dtype=torch.float32, device=dev) if lp is None else lp
+    for t, dt in ((ids, torch.int32), (gap, torch.float32), (lp, torch.float32)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous() and t.numel() == rows
+    kw = {}
+    if logp is not None:
+        assert logp.shape == logits.shape and logp.stride(1) == 1 and logp.dtype == torch.float32 and logp.is_cuda
+        kw = dict(logp=_ptr(logp), ld_logp=logp.stride(0) if rows > 1 else max(logp.stride(0), V))
+    _lib.call_struct("mi355_ctc_rows", "mi355_ctc_rows_args", _stream(), logits=_ptr(logits), ld=logits.stride(0) if rows > 1 else max(logits.stride(0), V),
+                     rows=rows, V=V, ids=_ptr(ids), gap=_ptr(gap), lp=_ptr(lp), **kw)
+    return ids, gap, lp
+
+
+def ctc_collapse(ids: torch.Tensor, *, lens: Optional[torch.Tensor] = None, skip: int = 0, blank: int = 0, return_frames: bool = False):
+    """Greedy CTC collapse of ``ids`` int32 [B, T] over the rows ``skip .. lens[b] - 1`` (``mi355_ctc_collapse``): repeats of the previous row's id
+    dropped, then blanks -> ``(tokens int32 [B, T], counts int32 [B])`` on the device, -1 behind ``counts[b]``; ``return_frames`` adds each kept id's row."""
+    assert ids.dim() == 2 and ids.stride(1) == 1 and ids.dtype == torch.int32 and ids.is_cuda
+    B, T = ids.shape
+    tokens = torch.empty((B, T), dtype=torch.int32, device=ids.device)
+    counts = torch.empty((B,), dtype=torch.int32, device=ids.device)
+    frames = torch.empty((B, T), dtype=torch.int32, device=ids.device) if return_frames else None
+    _lib.call_struct("mi355_ctc_collapse", "mi355_ctc_collapse_args", _stream(), ids=_ptr(ids), ld_ids=ids.stride(0) if B > 1 else max(ids.stride(0), T),
+                     lens=_lens_arg(lens, B), skip=skip, blank=blank, B=B, T=T, tokens=_ptr(tokens), counts=_ptr(counts), frames=_ptr(frames))
+    return (tokens, counts, frames) if return_frames else (tokens, counts)
+
+
 def sample(logits: torch.Tensor, out: torch.Tensor, *, V: Optional[int] = None, suppress_mask=None, history=None, n_hist: int = 0,
            hist_len=None, repetition_penalty: float = 1.0, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
            gumbel=None, done=None, done_token: int = 0, filtered=None):
