@@ -1361,6 +1361,100 @@ typedef struct {
 } mi355_ctc_collapse_args;
 int mi355_ctc_collapse(const mi355_ctc_collapse_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MossFormer2 SE 48K (sts/models/mossformer2_se): the token shift with ScaleNorm, the FLASH gated single-head attention (global linear term and
+ * grouped ReLU^2 term) and the gated FSMN memory (mossformer.hip).  Four entry points added to ABI 37 (new structs and functions only).
+ * Plain float32, channels-last [B, T, ld] views with explicit row (ld) and batch strides, in floats.  lens [B] (device, nullable => T) is clamped
+ * to [0, T]: rows t >= lens[b] READ as zero and are WRITTEN as zero.  No atomics, nothing allocated; every sum runs in an order that depends on
+ * neither the launch geometry, nor B, nor the other items' lengths: two calls on the same bytes give the same bits, and an item inside a ragged
+ * batch is bit-equal to that item alone.  Rows are 16-byte aligned (pointers multiples of 16 bytes, strides multiples of 4 floats).
+ * Where a contract says that two tensors must not alias, the entry point compares their base pointers only: views that overlap without sharing
+ * a base pointer are not detected and are the caller's duty.
+ * ------------------------------------------------------------------------------------------ */
+#define MI355_GAU_DIM 128         /* query / key width of the FLASH layer (to_qk's output) */
+#define MI355_GAU_GROUP 256       /* rows per attention group */
+#define MI355_GAU_ROPE_DIMS 32    /* leading columns that rotate, as the pairs (i, i + 16) */
+#define MI355_GAU_MAX_E 2048      /* widest v | u */
+#define MI355_GATED_FSMN_MAX_TAPS 63
+
+/* The token shift of FLASH_ShareA_FFConvM.__call__ (flash_sharea_ffconvm.py:134-156) and ScaleNorm (scalenorm.py:35-41) in one read and one
+ * write.  With s[b, t, c] = x[b, t - 1, c] for c < C / 2 (zero at t = 0) and x[b, t, c] for c >= C / 2 when shift != 0, s = x when shift == 0:
+ *   y[b, t, c] = s * (g / max(sqrt(sum_c s^2) * C^-1/2, eps)),   g = *g (device scalar) or 1 when g is NULL.
+ * An all-zero row gives exactly zero.  One wave per row: lane l adds the squares of its float4 pieces l, l + 64, ... in ascending order with
+ * fmaf, then the xor butterfly.  C % 8 == 0, 8 <= C <= 2048, else MI355_ERR_ARG without a launch.  y must not alias x when shift != 0. */
+typedef struct {
+  const float* x; int64_t x_bstride; int64_t ldx;
+  const float* g; float eps; int32_t shift;
+  const int32_t* lens;
+  int32_t B; int32_t T; int32_t C;
+  float* y; int64_t y_bstride; int64_t ldy;
+} mi355_shift_scalenorm_args;
+int mi355_shift_scalenorm(const mi355_shift_scalenorm_args* a, void* stream);
+
+/* The four heads of the FLASH layer are formed from qk [B, T, ldqk >= 128] (to_qk's output) wherever they are used (offsetscale.py:40-57,
+ * mossformerblock_gfsmn.py:61-63: nn.RoPE(dims = 32, traditional = False, base = 10000)):
+ *   head_h[t, i] = rope_t(qk[t, :] * gamma[h, :] + beta[h, :])[i],   h = 0 quad_q, 1 lin_q, 2 quad_k, 3 lin_k;   gamma, beta [4, 128]
+ *   rope_t(z)[i] = z[i] cos[t, i] - z[i + 16] sin[t, i],  rope_t(z)[i + 16] = z[i + 16] cos[t, i] + z[i] sin[t, i]  for i < 16;  z[i] for i >= 32
+ * with the host tables cos / sin [rope_rows >= T, 16] (device), cos[t, i] = cos(t * 10000^(-i / 16)); t is the row index inside the item.  The
+ * four products of a pair are rounded on their own (no contraction).
+ *
+ * mi355_gau_kv: the global linear-attention matrix of cal_attention (flash_sharea_ffconvm.py:320-363),
+ *   kv[b, d, e] = (sum_{t < lens[b]} lin_k[b, t, d] * vu[b, t, e]) / lens[b],   vu [B, T, ldvu >= E] (to_hidden's output, v | u), kv [B, 128, E].
+ * Each group of 256 rows leaves its partial sum (an fmaf chain over its rows in ascending order, on v_mfma_f32_32x32x2_f32) in
+ * ws [B, ceil(T / 256), 128, E] floats, caller-supplied; a second launch adds the partials of the groups below ceil(lens[b] / 256) in ascending
+ * group order and divides by lens[b].  lens[b] == 0 gives kv = 0.  E % 64 == 0, 64 <= E <= 2048, T <= rope_rows, else MI355_ERR_ARG. */
+typedef struct {
+  const float* qk; int64_t qk_bstride; int64_t ldqk;
+  const float* vu; int64_t vu_bstride; int64_t ldvu;
+  const float* gamma; const float* beta;
+  const float* rope_cos; const float* rope_sin; int32_t rope_rows;
+  const int32_t* lens;
+  int32_t B; int32_t T; int32_t E;
+  float* ws; int64_t ws_floats;                /* >= B * ceil(T / 256) * 128 * E */
+  float* kv; int64_t kv_bstride;               /* [B, 128, E], rows of E contiguous */
+} mi355_gau_kv_args;
+int mi355_gau_kv(const mi355_gau_kv_args* a, void* stream);
+
+/* cal_attention and the output gate (flash_sharea_ffconvm.py:170-188,244-301,365-378; flash_attention_kernels.py:107-132), non-causal.  For
+ * row t < lens[b] of group G = t / 256, over the keys j of the same group with j < lens[b], H = E / 2:
+ *   S[t, j]   = relu(sum_d quad_q[t, d] * quad_k[j, d] / 256)^2
+ *   A[t, e]   = sum_d lin_q[t, d] * kv[b, d, e] + sum_j S[t, j] * vu[j, e]      (the linear chain first, then the keys: the tile's fixed order)
+ *   out[t, c] = (A[t, H + c] * vu[t, c]) * sigmoid(A[t, c] * vu[t, H + c]),   c < H;   out [B, T, ldo >= H]
+ * The query tile of attn_tile.h: S^T = K Q^T and O^T += V^T P^T on v_mfma_f32_32x32x2_f32, P fed from the accumulator registers; the score
+ * tile never leaves the registers.  One workgroup owns 128 rows and cols columns of v with the same columns of u; cols = 0 lets the library
+ * choose, 32 / 64 / 128 (a divisor of H) pins it: the bits do not depend on it.  qk_dim must be 128, group 256 and causal 0, else
+ * MI355_ERR_UNSUPPORTED without a launch.  E % 64 == 0, 64 <= E <= 2048.  out must not alias vu. */
+typedef struct {
+  const float* qk; int64_t qk_bstride; int64_t ldqk;
+  const float* vu; int64_t vu_bstride; int64_t ldvu;
+  const float* kv; int64_t kv_bstride;
+  const float* gamma; const float* beta;
+  const float* rope_cos; const float* rope_sin; int32_t rope_rows;
+  const int32_t* lens;
+  int32_t B; int32_t T; int32_t E;
+  int32_t qk_dim; int32_t group; int32_t causal; int32_t cols;
+  float* out; int64_t out_bstride; int64_t ldo;
+} mi355_gau_attention_args;
+int mi355_gau_attention(const mi355_gau_attention_args* a, void* stream);
+
+/* Gated_FSMN.__call__ behind its projections (gated_fsmn.py:105-116) with UniDeepFsmn's memory (unideepfsmn.py:96-123):
+ *   y[b, t, c] = xv[b, t, c] * ((xu[b, t, c] + p[b, t, c]) + sum_{j < K} w[c, j] * p[b, t + j - (K - 1) / 2, c]) + res[b, t, c]
+ * p = fsmn.project's output, xu = to_u's, xv = to_v's, res = the block's input; rows of p outside [0, lens[b]) read as zero.  The tap sum is
+ * an fmaf chain from zero, j ascending; the last multiply-add is one fmaf.  w [C, K] float32 as mi355_dwconv takes it, K odd,
+ * K <= MI355_GATED_FSMN_MAX_TAPS, else MI355_ERR_ARG without a launch.  y may alias res (each element is read, then written, by one thread);
+ * y must not alias p. */
+typedef struct {
+  const float* p; int64_t p_bstride; int64_t ldp;
+  const float* xu; int64_t xu_bstride; int64_t ldxu;
+  const float* xv; int64_t xv_bstride; int64_t ldxv;
+  const float* res; int64_t res_bstride; int64_t ldres;
+  const float* w; int32_t K;
+  const int32_t* lens;
+  int32_t B; int32_t T; int32_t C;
+  float* y; int64_t y_bstride; int64_t ldy;
+} mi355_gated_fsmn_args;
+int mi355_gated_fsmn(const mi355_gated_fsmn_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

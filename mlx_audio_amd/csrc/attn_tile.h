@@ -1,5 +1,6 @@
 // The 32 x 32 query tile that flash_attn_kernel, flash_attn16_kernel (flash_attn.hip), relpos_attn_kernel (conformer.hip) and narrow_attn_kernel
-// (narrow_attn.hip) are built on, stated once.
+// (narrow_attn.hip) are built on, stated once; gau_attn_kernel (mossformer.hip) uses its orientation, C-row order and the two contraction steps
+// with ReLU^2 in place of the softmax step.
 //
 // Tiling.  One workgroup = 128 queries x one head, 4 waves x 32 queries.  K and V stream through LDS in stages of KB keys; the next stage's global
 // loads sit in registers (`prefetch`) over the current stage's math and go to LDS (`commit`) between two barriers.

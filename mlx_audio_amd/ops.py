@@ -1518,6 +1518,106 @@ def ctc_collapse(ids: torch.Tensor, *, lens: Optional[torch.Tensor] = None, skip
     return (tokens, counts, frames) if return_frames else (tokens, counts)
 
 
+GAU_DIM = 128            # MI355_GAU_DIM
+GAU_GROUP = 256          # MI355_GAU_GROUP
+GAU_ROPE_DIMS = 32       # MI355_GAU_ROPE_DIMS
+GAU_MAX_E = 2048         # MI355_GAU_MAX_E
+GATED_FSMN_MAX_TAPS = 63  # MI355_GATED_FSMN_MAX_TAPS
+
+
+def gau_rope_tables(rows: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(cos, sin)`` [rows, 16] float32 of ``nn.RoPE(dims=32, traditional=False, base=10000)``: the angle of row ``t``, pair ``i`` is
+    ``t * 10000^(-i / 16)``, computed in float64 on the host and rounded once."""
+    t = torch.arange(rows, dtype=torch.float64)[:, None]
+    inv = torch.pow(torch.tensor(10000.0, dtype=torch.float64), -torch.arange(GAU_ROPE_DIMS // 2, dtype=torch.float64) / (GAU_ROPE_DIMS // 2))
+    ang = t * inv[None, :]
+    cos, sin = torch.cos(ang).float().contiguous(), torch.sin(ang).float().contiguous()
+    return (cos, sin) if device is None else (cos.to(device), sin.to(device))
+
+
+def shift_scalenorm(x: torch.Tensor, y: torch.Tensor, *, g: Optional[torch.Tensor] = None, eps: float = 1e-8, shift: bool = True,
+                    lens: Optional[torch.Tensor] = None):
+    """``y = s * g / max(||s||_2 * C^-1/2, eps)`` per row (``mi355_shift_scalenorm``), ``s`` = ``x`` with the first half of its columns taken from the
+    row before (zero at row 0) when ``shift``, ``x`` itself otherwise.  ``x`` / ``y`` channels-last views [B, T, C], ``C`` a multiple of 8 up to 2048;
+    ``g`` a one-element device tensor or None (= 1).  Rows at and beyond ``lens[b]`` come back zero."""
+    B, T, C, xbs, ldx = _nlc(x)
+    By, Ty, Cy, ybs, ldy = _nlc(y)
+    assert (By, Ty, Cy) == (B, T, C)
+    if g is not None:
+        assert g.dtype == torch.float32 and g.is_cuda and g.numel() == 1
+    _lib.call_struct("mi355_shift_scalenorm", "mi355_shift_scalenorm_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, g=_ptr(g), eps=eps,
+                     shift=int(shift), lens=_lens_arg(lens, B), B=B, T=T, C=C, y=_ptr(y), y_bstride=ybs, ldy=ldy)
+    return y
+
+
+def _gau_common(qk, vu, gamma, beta, rope):
+    B, T, Cq, qbs, ldq = _nlc(qk)
+    Bv, Tv, E, vbs, ldv = _nlc(vu)
+    assert (Bv, Tv) == (B, T) and Cq == GAU_DIM, (qk.shape, vu.shape)
+    for t in (gamma, beta):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (4, GAU_DIM)
+    cos, sin = rope
+    for t in (cos, sin):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == GAU_ROPE_DIMS // 2
+    assert cos.shape == sin.shape
+    return B, T, E, dict(qk=_ptr(qk), qk_bstride=qbs, ldqk=ldq, vu=_ptr(vu), vu_bstride=vbs, ldvu=ldv, gamma=_ptr(gamma), beta=_ptr(beta),
+                         rope_cos=_ptr(cos), rope_sin=_ptr(sin), rope_rows=cos.shape[0], B=B, T=T, E=E)
+
+
+def gau_kv_workspace_floats(B: int, T: int, E: int) -> int:
+    return B * ((T + GAU_GROUP - 1) // GAU_GROUP) * GAU_DIM * E
+
+
+def gau_kv(qk: torch.Tensor, vu: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rope, *, lens: Optional[torch.Tensor] = None,
+           kv: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """``kv[b] = lin_k[b]^T vu[b] / lens[b]`` [B, 128, E] over the rows below ``lens[b]`` (``mi355_gau_kv``): the global linear-attention matrix of
+    the FLASH layer.  ``qk`` [B, T, 128] and ``vu`` [B, T, E] channels-last views, ``gamma`` / ``beta`` [4, 128], ``rope`` = ``gau_rope_tables``
+    with at least ``T`` rows.  ``ws``: at least ``gau_kv_workspace_floats(B, T, E)`` floats for the per-group partial sums."""
+    B, T, E, kw = _gau_common(qk, vu, gamma, beta, rope)
+    if kv is None:
+        kv = torch.empty((B, GAU_DIM, E), dtype=torch.float32, device=qk.device)
+    assert kv.dtype == torch.float32 and kv.is_cuda and tuple(kv.shape) == (B, GAU_DIM, E) and kv[0].is_contiguous()
+    need = gau_kv_workspace_floats(B, T, E)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.float32, device=qk.device)
+    assert ws.dtype == torch.float32 and ws.is_cuda and ws.is_contiguous()
+    _lib.call_struct("mi355_gau_kv", "mi355_gau_kv_args", _stream(), lens=_lens_arg(lens, B), ws=_ptr(ws), ws_floats=ws.numel(), kv=_ptr(kv),
+                     kv_bstride=kv.stride(0) if B > 1 else GAU_DIM * E, **kw)
+    return kv
+
+
+def gau_attention(qk: torch.Tensor, vu: torch.Tensor, kv: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rope, out: torch.Tensor, *,
+                  lens: Optional[torch.Tensor] = None, causal: bool = False, qk_dim: int = GAU_DIM, group: int = GAU_GROUP, cols: int = 0):
+    """The FLASH layer's attention and output gate (``mi355_gau_attention``): per group of 256 rows ``relu(quad_q quad_k^T / 256)^2 vu`` plus
+    ``lin_q kv``, then ``out = (A_u * v) * sigmoid(A_v * u)`` [B, T, E / 2].  Arguments as ``gau_kv``; ``kv`` its result.  Rows at and beyond
+    ``lens[b]`` come back zero.  ``causal``, another ``qk_dim`` or ``group`` are refused; ``cols`` (0 = the library chooses) pins how many columns of
+    ``v`` one workgroup owns and never changes a bit of the result."""
+    B, T, E, kw = _gau_common(qk, vu, gamma, beta, rope)
+    Bo, To, Ho, obs, ldo = _nlc(out)
+    assert (Bo, To, Ho) == (B, T, E // 2)
+    assert kv.dtype == torch.float32 and kv.is_cuda and tuple(kv.shape) == (B, GAU_DIM, E) and kv[0].is_contiguous()
+    _lib.call_struct("mi355_gau_attention", "mi355_gau_attention_args", _stream(), kv=_ptr(kv), kv_bstride=kv.stride(0) if B > 1 else GAU_DIM * E,
+                     lens=_lens_arg(lens, B), qk_dim=qk_dim, group=group, causal=int(causal), cols=cols, out=_ptr(out), out_bstride=obs, ldo=ldo, **kw)
+    return out
+
+
+def gated_fsmn(p: torch.Tensor, xu: torch.Tensor, xv: torch.Tensor, res: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *,
+               lens: Optional[torch.Tensor] = None):
+    """``y = xv * (xu + p + sum_j w[:, j] * p[t + j - (K - 1) / 2]) + res`` (``mi355_gated_fsmn``): the gated FSMN memory of MossFormer2.  All five
+    tensors channels-last views [B, T, C]; ``w`` [C, K] float32 (K odd, <= ``GATED_FSMN_MAX_TAPS``).  ``p`` reads as zero outside ``[0, lens[b])``;
+    rows at and beyond ``lens[b]`` come back zero.  ``y`` may be ``res``."""
+    B, T, C, pbs, ldp = _nlc(p)
+    kw = {}
+    for name, t in (("xu", xu), ("xv", xv), ("res", res), ("y", y)):
+        Bt, Tt, Ct, bs, ld = _nlc(t)
+        assert (Bt, Tt, Ct) == (B, T, C), (name, t.shape)
+        kw.update({name: _ptr(t), name + "_bstride": bs, "ld" + name: ld})
+    assert w.dim() == 2 and w.shape[0] == C and w.is_contiguous() and w.dtype == torch.float32 and w.is_cuda
+    _lib.call_struct("mi355_gated_fsmn", "mi355_gated_fsmn_args", _stream(), p=_ptr(p), p_bstride=pbs, ldp=ldp, w=_ptr(w), K=w.shape[1],
+                     lens=_lens_arg(lens, B), B=B, T=T, C=C, **kw)
+    return y
+
+
 def sample(logits: torch.Tensor, out: torch.Tensor, *, V: Optional[int] = None, suppress_mask=None, history=None, n_hist: int = 0,
            hist_len=None, repetition_penalty: float = 1.0, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
            gumbel=None, done=None, done_token: int = 0, filtered=None):

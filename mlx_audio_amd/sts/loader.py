@@ -18,8 +18,10 @@ MODEL_REMAPPING = {
 
 
 def get_available_models() -> List[str]:
+    """The directories under ``models`` that are values of ``MODEL_REMAPPING``, i.e. the families ``load_model`` routes.  A family that is loaded
+    through its own class (``MossFormer2SEModel.from_pretrained``; Mel-Band RoFormer is a module file) is not listed."""
     d = Path(__file__).parent / "models"
-    return sorted(p.name for p in d.iterdir() if p.is_dir() and not p.name.startswith("__"))
+    return sorted(p.name for p in d.iterdir() if p.is_dir() and p.name in MODEL_REMAPPING.values())
 
 
 def load_model(model_path: Union[str, Path], lazy: bool = False, strict: bool = False, **kwargs: Any):
