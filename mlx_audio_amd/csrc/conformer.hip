@@ -4,6 +4,7 @@
 // the 3 x 3 / stride 2 convs of DwStridingSubsampling (conformer.py:174-207).  All three are plain float32 with a fixed summation order: no atomics,
 // and nothing in the order depends on the launch geometry, so two calls on the same bytes give the same bits.
 #include "attn_tile.h"
+#include "dw_window.h"
 
 namespace {
 
@@ -132,47 +133,34 @@ __global__ __launch_bounds__(256) void relpos_attn_kernel(const mi355_relpos_att
 // ---------------------------------------------------------------------------------------------------- GLU -> depthwise conv -> (BatchNorm) -> SiLU
 __device__ __forceinline__ float sigmoid_f32(const float x) { return 1.0f / (1.0f + expf(-x)); }
 
-constexpr int kGluRun = 32;   // consecutive time steps per thread (fsmn_memory_kernel's shape: s3.hip)
-
-// One thread = one channel x kGluRun time steps; the 64 lanes of a wave are 64 adjacent channels (every row access is one 256-byte request for each
-// half of x), the four waves of a workgroup four consecutive runs.  The gated window and the channel's taps live in registers.  KMAX is the
-// register window's tap count: shorter kernels are centred in it (0 * finite adds nothing to the sum).
+// The register-window run of dw_window.h over x * sigmoid(gate) (the two halves of a row of x: two 256-byte requests per row access), from the bias.
 template <int KMAX>
 __global__ __launch_bounds__(256) void glu_dwconv_silu_kernel(const mi355_glu_dwconv_silu_args a) {
-  constexpr int kHalf = (KMAX - 1) / 2, kWin = kGluRun + KMAX - 1;
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int t0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * kGluRun;
-  const int b = blockIdx.z;
-  if (c >= a.C || t0 >= a.L) return;
-  const int len = a.lens ? min(max(a.lens[b], 0), a.L) : a.L;
+  int c, t0, b;
+  if (!dw_decode(a.C, a.L, c, t0, b)) return;
+  const int len = dw_len(a.lens, b, a.L);
   const float* xb = a.x + (int64_t)b * a.x_bstride + c;
   float w[KMAX];
-  const int shift = kHalf - (a.K - 1) / 2;
+  const int shift = dw_tap_shift<KMAX>(a.K);
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) {
     const int k = j - shift;
     w[j] = (k >= 0 && k < a.K) ? a.w[(int64_t)c * a.K + k] : 0.f;
   }
   const float bias = a.b ? a.b[c] : 0.f;
-  float win[kWin];
+  float win[kRun + KMAX - 1];
+  const auto row = [xb, ldx = a.ldx, C = a.C](const int r) {
+    const float* xr = xb + (int64_t)r * ldx;
+    return xr[0] * sigmoid_f32(xr[C]);
+  };
 #pragma unroll
-  for (int i = 0; i < kWin; ++i) {
-    const int r = t0 - kHalf + i;
-    float g = 0.f;
-    if (r >= 0 && r < len) {   // rows at or beyond lens[b] (<= L) and outside [0, L) are zero: never dereferenced
-      const float* xr = xb + (int64_t)r * a.ldx;
-      g = xr[0] * sigmoid_f32(xr[a.C]);
-    }
-    win[i] = g;
-  }
+  for (int i = 0; i < kRun + KMAX - 1; ++i) win[i] = dw_window_row<KMAX>(i, t0, len, row);
   float* yb = a.y + (int64_t)b * a.y_bstride + c;
 #pragma unroll
-  for (int i = 0; i < kGluRun; ++i) {
+  for (int i = 0; i < kRun; ++i) {
     const int t = t0 + i;
     if (t >= a.L) break;
-    float z = bias;
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) z = fmaf(w[j], win[i + j], z);   // taps in order k = 0 .. K - 1
+    const float z = dw_tap_sum<KMAX>(w, win, i, bias);
     yb[(int64_t)t * a.ldy] = t < len ? z * sigmoid_f32(z) : 0.f;
   }
 }
@@ -252,9 +240,8 @@ extern "C" int mi355_glu_dwconv_silu(const mi355_glu_dwconv_silu_args* ap, void*
   MI355_REQUIRE(a.K >= 1 && a.K <= MI355_GLU_DWCONV_MAX_TAPS && (a.K & 1) == 1, "glu_dwconv_silu: K must be odd and <= %d (got %d)", MI355_GLU_DWCONV_MAX_TAPS, a.K);
   MI355_REQUIRE(a.ldx >= 2 * a.C && a.ldy >= a.C, "glu_dwconv_silu: a row stride is too small (x rows hold 2 C values)");
   MI355_REQUIRE((const void*)a.y != (const void*)a.x, "glu_dwconv_silu: y must not alias x (a step reads its neighbours' values)");
-  const int64_t gy = ((int64_t)a.L + 4 * kGluRun - 1) / (4 * kGluRun);
-  MI355_REQUIRE(gy <= 65535, "glu_dwconv_silu: sequence too long");
-  const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)gy, (unsigned)a.B);
+  dim3 grid;
+  if (const int rc = dw_grid("glu_dwconv_silu", a.C, a.L, a.B, &grid)) return rc;
   MI355_CLEAR_ERROR();
   if (a.K <= 9) hipLaunchKernelGGL(glu_dwconv_silu_kernel<9>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(glu_dwconv_silu_kernel<MI355_GLU_DWCONV_MAX_TAPS>, grid, dim3(256), 0, (hipStream_t)stream, a);

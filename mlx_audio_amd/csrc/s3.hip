@@ -3,40 +3,30 @@
 // value projection, masked before and after, plus the masked values), FSQCodebook.encode (:82-96: Linear(n_state, 8) -> tanh -> * 0.999 ->
 // round half to even -> + 1 -> base-3 digits).  Both are plain float32 with a fixed summation order: no atomics, and nothing in the order
 // depends on the launch geometry, so two calls on the same bytes give the same bits.
-#include "common.h"
+#include "dw_window.h"
 
 namespace {
 
 constexpr int kTaps = MI355_FSMN_MAX_TAPS;   // the register window is sized for the reference's 31 taps; shorter kernels are centred in it
 constexpr int kHalf = (kTaps - 1) / 2;
-constexpr int kRun = 32;                     // consecutive time steps per thread: a value of v is requested (kRun + kTaps - 1) / kRun = 1.94 times,
-                                             // the second time from L2 (the neighbouring run's workgroup is resident at the same time)
-constexpr int kWin = kRun + kTaps - 1;
 
-// One thread = one channel x kRun time steps; the 64 lanes of a wave are 64 adjacent channels (every row access is one 256-byte request), the four
-// waves of a workgroup four consecutive runs.  The kWin values of the window and the channel's taps live in registers (all indices are compile-time
-// constants after unrolling).  grid (ceil(C / 64), ceil(L / (4 kRun)), B): the channel groups of one run are neighbours in launch order.
+// The register-window run of dw_window.h over the value projection, plus the values themselves and the residual stream.
 __global__ __launch_bounds__(256) void fsmn_memory_kernel(const mi355_fsmn_memory_args a) {
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int t0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * kRun;
-  const int b = blockIdx.z;
-  if (c >= a.C || t0 >= a.L) return;
-  const int len = a.lens ? min(max(a.lens[b], 0), a.L) : a.L;
+  int c, t0, b;
+  if (!dw_decode(a.C, a.L, c, t0, b)) return;
+  const int len = dw_len(a.lens, b, a.L);
   const float* vb = a.v + (int64_t)b * a.v_bstride + c;
-  // taps: w[c][j] sits at window offset j + (kHalf - left), left = (K - 1) / 2; the other offsets are zero (0 * finite adds nothing to the sum)
   float w[kTaps];
-  const int shift = kHalf - (a.K - 1) / 2;
+  const int shift = dw_tap_shift<kTaps>(a.K);
 #pragma unroll
   for (int j = 0; j < kTaps; ++j) {
     const int k = j - shift;
     w[j] = (k >= 0 && k < a.K) ? a.w[(int64_t)c * a.K + k] : 0.f;
   }
-  float win[kWin];
+  float win[kRun + kTaps - 1];
+  const auto row = [vb, ldv = a.ldv](const int r) { return vb[(int64_t)r * ldv]; };
 #pragma unroll
-  for (int i = 0; i < kWin; ++i) {
-    const int r = t0 - kHalf + i;
-    win[i] = (r >= 0 && r < len) ? vb[(int64_t)r * a.ldv] : 0.f;   // rows at or beyond lens[b] (<= L) and outside [0, L) read as zero: never dereferenced
-  }
+  for (int i = 0; i < kRun + kTaps - 1; ++i) win[i] = dw_window_row<kTaps>(i, t0, len, row);
   // the residual stream is requested WITH the window, before any store: y may be add, so behind a store the compiler must keep every later load of
   // add in program order -- one exposed memory round trip per time step
   const float* ab = a.add ? a.add + (int64_t)b * a.add_bstride + c : nullptr;
@@ -48,9 +38,7 @@ __global__ __launch_bounds__(256) void fsmn_memory_kernel(const mi355_fsmn_memor
   for (int i = 0; i < kRun; ++i) {
     const int t = t0 + i;
     if (t >= a.L) break;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < kTaps; ++j) s = fmaf(w[j], win[i + j], s);   // taps in order j = 0 .. K - 1
+    float s = dw_tap_sum<kTaps>(w, win, i, 0.f);
     s += win[i + kHalf];
     float o = res[i];
     if (t < len) o += s;
@@ -129,10 +117,10 @@ extern "C" int mi355_fsmn_memory(const mi355_fsmn_memory_args* ap, void* stream)
   MI355_REQUIRE(a.K >= 1 && a.K <= kTaps && (a.K & 1) == 1, "fsmn_memory: K must be odd and <= %d (got %d)", kTaps, a.K);
   MI355_REQUIRE(a.ldv >= a.C && a.ldy >= a.C && (!a.add || a.add_ld >= a.C), "fsmn_memory: a row stride is smaller than C");
   MI355_REQUIRE((const void*)a.y != (const void*)a.v, "fsmn_memory: y must not alias v (a step reads its neighbours' values)");
-  const int64_t gy = ((int64_t)a.L + 4 * kRun - 1) / (4 * kRun);
-  MI355_REQUIRE(gy <= 65535, "fsmn_memory: sequence too long");
+  dim3 grid;
+  if (const int rc = dw_grid("fsmn_memory", a.C, a.L, a.B, &grid)) return rc;
   MI355_CLEAR_ERROR();
-  hipLaunchKernelGGL(fsmn_memory_kernel, dim3((unsigned)((a.C + 63) / 64), (unsigned)gy, (unsigned)a.B), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(fsmn_memory_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   MI355_LAUNCH_CHECK("fsmn_memory");
   return MI355_OK;
 }
