@@ -403,6 +403,47 @@ typedef struct {
 int mi355_narrow_attention(const mi355_narrow_attention_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Moonshine (stt/models/moonshine/moonshine.py): attention for heads of 36 - 60 (tiny: 8 x 36, base: 8 x 52) and the partial
+ * rotary embedding in front of it.  Two entry points added to ABI 37 (new structs and functions only; no existing layout
+ * changed).  Plain float32, a fixed summation order: two calls on the same bytes give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+/* MoonshineAttention.__call__ behind the projections: self, cross (Tq != Tk) and causal attention with grouped kv heads.
+ * Head h sits at columns [h dh, (h + 1) dh) of the q / out rows and reads kv head h / (heads / kv_heads) of the k / v rows.
+ * With nq = lens_q[b] (NULL: Tq) and nk = lens_k[b] (NULL: Tk), for i < nq:
+ *   out_i = sum_j softmax_j(scale * q_i . k_j) v_j over the visible keys: j < nk, and under `causal` j <= i + (nk - nq)
+ * (the queries are the last nq positions).  Invisible keys have probability exactly 0; a query with no visible key gives a zero
+ * row; output rows nq <= i < Tq are written as zeros.  dh 36, 40, 44, 48, 52, 56 or 60; MI355_ERR_ARG without a launch for any
+ * other dh, for Tq < 1 or Tk < 1, for heads % kv_heads != 0, for a row stride below heads * dh (kv_heads * dh for k / v) and for
+ * rows that are not 16-byte aligned (strides multiples of 4).  Tq <= 4 runs one wavefront per (query, head, item) over any Tk
+ * (the decode step); larger Tq runs 128-query tiles.  No [Tq, Tk] matrix is written to memory and there is no workspace. */
+typedef struct {
+  const float* q; int64_t q_bstride; int32_t ldq;        /* [B, Tq, ldq] */
+  const float* k; int64_t k_bstride; int32_t ldk;        /* [B, Tk, ldk] */
+  const float* v; int64_t v_bstride; int32_t ldv;
+  const int32_t* lens_q; const int32_t* lens_k;          /* [B] nullable => Tq / Tk */
+  int32_t B; int32_t Tq; int32_t Tk; int32_t heads; int32_t kv_heads; int32_t dh; int32_t causal; float scale;
+  float* out; int64_t out_bstride; int32_t ldo;          /* [B, Tq, ldo] */
+} mi355_mid_attention_args;
+int mi355_mid_attention(const mi355_mid_attention_args* a, void* stream);
+
+/* apply_rotary_pos_emb (moonshine.py:35-58): for every head of dh channels and every pair i < rot / 2
+ *   (x[2i], x[2i+1]) -> (x[2i] c_i - x[2i+1] s_i, x[2i+1] c_i + x[2i] s_i),  c_i, s_i = cos / sin_table[(pos0 + l) * (rot / 2) + i],
+ * each product rounded on its own; channels rot .. dh - 1 are copied.  x [B, L, ldx] holds `heads` heads from column 0; y may be x
+ * (in place) or a cache slot.  The optional second operand (x2 -> y2, heads2 heads: the k heads into their cache row) is handled
+ * by the same launch with the same positions.  Rows l >= lens[b] are left untouched.  rot even, 2 <= rot <= dh, dh % 4 == 0;
+ * MI355_ERR_ARG without a launch when pos0 + L > rope_rows (positions past the tables). */
+typedef struct {
+  const float* x; int64_t x_bstride; int32_t ldx; int32_t heads;
+  float* y; int64_t y_bstride; int32_t ldy;
+  const float* x2; int64_t x2_bstride; int32_t ldx2; int32_t heads2;   /* nullable */
+  float* y2; int64_t y2_bstride; int32_t ldy2;
+  int32_t dh; int32_t rot; int32_t B; int32_t L; int32_t pos0; int32_t rope_rows;
+  const int32_t* lens;                                   /* [B] nullable => L */
+  const float* cos_table; const float* sin_table;        /* [rope_rows, rot / 2] */
+} mi355_partial_rope_args;
+int mi355_partial_rope(const mi355_partial_rope_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bidirectional LSTM recurrence (the x-projection is a conv_gemm).
  * Replaces the per-time-step Python loops of LSTM._forward_direction/_backward_direction
  * (modules.py:150-240): gates i,f,g,o; c = f*c + i*g; h = o*tanh(c).

@@ -1,5 +1,5 @@
-// The 32 x 32 query tile that flash_attn_kernel, flash_attn16_kernel (flash_attn.hip), relpos_attn_kernel (conformer.hip) and narrow_attn_kernel
-// (narrow_attn.hip) are built on, stated once; gau_attn_kernel (mossformer.hip) uses its orientation, C-row order and the two contraction steps
+// The 32 x 32 query tile that flash_attn_kernel, flash_attn16_kernel (flash_attn.hip), relpos_attn_kernel (conformer.hip), narrow_attn_kernel
+// (narrow_attn.hip) and mid_attn_kernel (mid_attn.hip) are built on, stated once; gau_attn_kernel (mossformer.hip) uses its orientation, C-row order and the two contraction steps
 // with ReLU^2 in place of the softmax step.
 //
 // Tiling.  One workgroup = 128 queries x one head, 4 waves x 32 queries.  K and V stream through LDS in stages of KB keys; the next stage's global
@@ -25,6 +25,7 @@
 //   k_start[b] <= j < len_k,   causal: j <= qpos,   window W > 0: j > qpos - W.
 // Invisible keys get probability exactly 0 (the reference adds -1e9 / -inf style masks: identical after softmax); a query with no visible key
 // gives a zero row.  relpos and narrow see the keys j < lens[b] and nothing else, so key kb of every stage they run is valid (EMPTY = false below).
+// mid_attn_kernel applies the rule without k_start and window (its own args struct), with EMPTY = true.
 //
 // flash_attn16_kernel shares the tile, the key range, the visibility rule, the C-row order and the output store, but NOT attn_online_softmax: its
 // VALU-bound softmax skips the mask on interior blocks and the rescale when no maximum moved (both wave-uniform) and calls the bare v_exp_f32.

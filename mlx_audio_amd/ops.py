@@ -1415,6 +1415,71 @@ def narrow_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: tor
     return out
 
 
+MID_ATTENTION_WIDTHS = (36, 40, 44, 48, 52, 56, 60)
+MID_ATTENTION_FEW_TQ = 4   # Tq up to here runs one wavefront per (query, head, item): the decode step
+
+
+def mid_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, heads: int, dh: int, kv_heads: Optional[int] = None,
+                  scale: Optional[float] = None, causal: bool = False, lens_q: Optional[torch.Tensor] = None, lens_k: Optional[torch.Tensor] = None,
+                  check_lens: bool = True):
+    """``out_i = sum_j softmax_j(scale q_i . k_j) v_j`` over the visible keys (``mi355_mid_attention``): attention for heads of 36 - 60 (Moonshine:
+    8 x 36 and 8 x 52), self or cross (``Tq != Tk``), grouped kv heads, optional causal form.  ``q`` / ``out`` channels-last views
+    [B, Tq, >= heads * dh], ``k`` / ``v`` [B, Tk, >= kv_heads * dh] (thirds of a fused buffer, a cache slice, or contiguous).  Key ``j`` is visible
+    iff ``j < lens_k[b]`` and, under ``causal``, ``j <= i + (lens_k[b] - lens_q[b])``.  Rows at and beyond ``lens_q[b]`` come back zero; ``lens_q`` is not checked: the kernel clamps it to ``[0, Tq]``.  Every
+    ``lens_k[b]`` must be in ``[1, Tk]``: checked here with one device read, which a caller that built the lengths from host integers it has
+    already checked turns off (``check_lens=False``)."""
+    B, Tq, C, qbs, ldq = _nlc(q)
+    Bk, Tk, Ck, kbs, ldk = _nlc(k)
+    Bv, Tv, Cv, vbs, ldv = _nlc(v)
+    Bo, To, Co, obs, ldo = _nlc(out)
+    kvh = heads if kv_heads is None else kv_heads
+    assert Bk == B and (Bv, Tv) == (B, Tk) and (Bo, To) == (B, Tq) and min(C, Co) >= heads * dh and min(Ck, Cv) >= kvh * dh
+    if lens_k is not None and check_lens:
+        _lens_arg(lens_k, B)
+        lo, hi = int(lens_k.min()), int(lens_k.max())
+        if lo < 1 or hi > Tk:
+            raise _lib.Mi355Error(f"mid_attention: lens_k must lie in [1, Tk = {Tk}] (got min {lo}, max {hi})")
+    _lib.call_struct("mi355_mid_attention", "mi355_mid_attention_args", _stream(), q=_ptr(q), q_bstride=qbs, ldq=ldq, k=_ptr(k), k_bstride=kbs, ldk=ldk,
+                     v=_ptr(v), v_bstride=vbs, ldv=ldv, lens_q=_lens_arg(lens_q, B), lens_k=_lens_arg(lens_k, B), B=B, Tq=Tq, Tk=Tk, heads=heads,
+                     kv_heads=kvh, dh=dh, causal=int(causal), scale=dh ** -0.5 if scale is None else scale, out=_ptr(out), out_bstride=obs, ldo=ldo)
+    return out
+
+
+def moonshine_rope_tables(rot: int, rows: int, *, base: float = 10000.0, pos0: int = 0, device=None):
+    """(cos, sin) float32 [rows, rot / 2] for positions ``pos0 .. pos0 + rows - 1``, computed as the reference's rotary embedding computes them
+    (moonshine.py:35-58): ``inv_freq = 1 / base ** (arange(0, rot, 2) / rot)`` in float32, ``float32(pos) * inv_freq``, then cos / sin in float32.
+    As many rows as the call needs: ``max_position_embeddings`` bounds nothing in the reference."""
+    assert rot >= 2 and rot % 2 == 0 and rows >= 1
+    inv_freq = (np.float32(1.0) / np.power(np.float32(base), np.arange(0, rot, 2, dtype=np.float32) / np.float32(rot))).astype(np.float32)
+    ang = np.arange(pos0, pos0 + rows, dtype=np.float32)[:, None] * inv_freq[None, :]
+    cos, sin = torch.from_numpy(np.cos(ang).astype(np.float32)), torch.from_numpy(np.sin(ang).astype(np.float32))
+    return (cos, sin) if device is None else (cos.to(device), sin.to(device))
+
+
+def partial_rope(x: torch.Tensor, y: torch.Tensor, *, heads: int, dh: int, rot: int, cos: torch.Tensor, sin: torch.Tensor, pos0: int = 0,
+                 lens: Optional[torch.Tensor] = None, second: Optional[tuple] = None):
+    """Rotary embedding on the first ``rot`` channels of every head, interleaved pairs (``mi355_partial_rope``): ``x`` [B, L, >= heads * dh] into
+    ``y`` (``y is x``: in place; or a cache slot); channels ``rot .. dh - 1`` are copied.  Row ``l`` takes row ``pos0 + l`` of the ``cos`` / ``sin``
+    tables [rows, rot / 2] (``moonshine_rope_tables``); positions past the tables are refused.  ``second = (x2, y2, heads2)``: another operand (the
+    k heads, into their cache row) in the same launch.  Rows at and beyond ``lens[b]`` are left untouched."""
+    B, L, C, xbs, ldx = _nlc(x)
+    By, Ly, Cy, ybs, ldy = _nlc(y)
+    assert (By, Ly) == (B, L) and min(C, Cy) >= heads * dh
+    assert cos.dim() == 2 and cos.shape == sin.shape and cos.shape[1] == rot // 2 and cos.is_contiguous() and sin.is_contiguous()
+    assert cos.dtype == sin.dtype == torch.float32 and cos.is_cuda and sin.is_cuda
+    kw = {}
+    if second is not None:
+        x2, y2, heads2 = second
+        B2, L2, C2, x2bs, ldx2 = _nlc(x2)
+        By2, Ly2, Cy2, y2bs, ldy2 = _nlc(y2)
+        assert (B2, L2) == (B, L) and (By2, Ly2) == (B, L) and min(C2, Cy2) >= heads2 * dh
+        kw = dict(x2=_ptr(x2), x2_bstride=x2bs, ldx2=ldx2, heads2=heads2, y2=_ptr(y2), y2_bstride=y2bs, ldy2=ldy2)
+    _lib.call_struct("mi355_partial_rope", "mi355_partial_rope_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, heads=heads, y=_ptr(y),
+                     y_bstride=ybs, ldy=ldy, dh=dh, rot=rot, B=B, L=L, pos0=pos0, rope_rows=cos.shape[0], lens=_lens_arg(lens, B),
+                     cos_table=_ptr(cos), sin_table=_ptr(sin), **kw)
+    return y
+
+
 def glu_dwconv_silu(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, *, lens: Optional[torch.Tensor] = None):
     """``silu(b + sum_k w[:, k] * g[t + k - (K - 1) / 2])`` with ``g = x[..., :C] * sigmoid(x[..., C:])`` (``mi355_glu_dwconv_silu``): the middle of the
     Conformer's convolution module, ``x`` [B, L, 2 C] -> ``y`` [B, L, C]; ``w`` [C, K] (K odd, <= ``GLU_DWCONV_MAX_TAPS``) and ``b`` [C] carry the
