@@ -720,6 +720,28 @@ typedef struct {
 } mi355_conv_post_istft_args;
 int mi355_conv_post_istft(const mi355_conv_post_istft_args* a, void* stream);
 
+/* One up-sampler of the generator in ONE dedicated launch (new struct and function only; ABI stays 37): `x = leaky_relu(x, 0.1); x = ups[i](x);
+ * x = x + x_source` (istftnet.py:161-166, :811-826) -- i.e. the polyphase mi355_conv_gemm call (pre_act = LEAKY, K / u = 2 taps, pad = 1,
+ * res = x_source, up_s = u, up_p = p, up_cout = Cout, up_row_off = row_off, precision 2) on a kernel whose workgroups own a block of input rows
+ * and ALL u * Cout columns of it, so the activation window is loaded, activated and split once.  x [B, L, Cin] float32 (rows 16-byte aligned),
+ * w / bias: the polyphase bf16 image of mi355_pack_conv_weight_host ([u * Cout, 2, Cin], ops.pack_conv_transpose) and the fp32 bias [Cout]
+ * (nullable); res, y [B, L * u + row_off, Cout].
+ *   y[b, row_off + u m + phase - p, :] = sum over taps leaky(x[b, m - 1 + tap, :]) W[phase, tap] + bias + res[b, same row, :]
+ * for the output rows [row_off, row_off + lens[b] * u); input rows >= lens[b] read as zero AFTER the LeakyReLU, output rows beyond are left
+ * untouched.  row_off = 1 (the last stage, whose output carries one zero left-pad row): y[b, 0, :] = res[b, 0, :] as well.  Per output value the
+ * arithmetic and its order are those of mi355_conv_gemm's wave-specialised kernel (bf16 hi + lo passes, chunk -> tap order, bias, residual):
+ * bit-equal results; the path does not depend on B or L.
+ * Supported: (Cin, Cout, u) = (512, 256, 10) or (256, 128, 6), K == 2 u, p == (K - u) / 2, row_off 0 / 1, precision == 2; anything else returns
+ * MI355_ERR_UNSUPPORTED without a launch (the caller keeps mi355_conv_gemm). */
+typedef struct {
+  const float* x; int64_t x_bstride; int32_t ldx; int32_t Cin; int32_t L; const int32_t* lens; int32_t B;
+  const uint16_t* w; const float* bias; int32_t Cout; int32_t K; int32_t u; int32_t p; int32_t row_off;
+  float slope; int32_t precision;
+  const float* res; int64_t res_bstride; int32_t ldr;
+  float* y; int64_t y_bstride; int32_t ldy;
+} mi355_upsample_polyphase_args;
+int mi355_upsample_polyphase(const mi355_upsample_polyphase_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * mlx_audio.dsp (dsp.py): batched STFT / iSTFT for arbitrary n_fft (mixed-radix 2/3/4/5 +
  * generic-prime Stockham FFT staged in LDS) and the fused |X|^2 -> mel -> log front ends.

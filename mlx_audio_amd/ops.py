@@ -1853,6 +1853,53 @@ def conv_post_istft(x: torch.Tensor, pc: PackedConv, n_fft: int, hop: int, windo
     return istft_head(post, n_fft, hop, window, audio, lens=lens)
 
 
+# (Cin, Cout, stride) instantiations of mi355_upsample_polyphase (the header's list) -> GEMM rows a workgroup owns (upsample_poly.hip)
+UPSAMPLE_POLY_SHAPES = {(512, 256, 10): 32, (256, 128, 6): 64}
+
+
+def upsample_polyphase_eligible(pc: PackedConv, stride: int, *, pre_act: int = ACT_LEAKY, precision: int = 2, res=True, pre_fq=None) -> bool:
+    """Up-samplers ``mi355_upsample_polyphase`` takes: a bf16 polyphase image (``pack_conv_transpose``) with two taps per phase and one of the
+    instantiated (Cin, Cout, stride) sets, a LeakyReLU prologue and a residual.  Nothing here looks at the batch or at the length."""
+    return (pc.k == 2 and stride > 0 and pc.cout % stride == 0 and (pc.cin, pc.cout // stride, stride) in UPSAMPLE_POLY_SHAPES
+            and pre_act == ACT_LEAKY and precision == 2 and not pc.f16 and not pc.mx and res is not None and pre_fq is None)
+
+
+def upsample_polyphase(x: torch.Tensor, pc: PackedConv, res: torch.Tensor, y: torch.Tensor, stride: int, *, row_off: int = 0, lens=None,
+                       pre_act: int = ACT_LEAKY, pre_slope: float = 0.1, precision: int = 2, pre_fq=None):
+    """One generator up-sampler: ``y[:, row_off:] = conv_transpose1d(leaky_relu(x), stride, K = 2 stride, padding = stride / 2) + res[:, row_off:]``
+    (and ``y[:, 0] = res[:, 0]`` for ``row_off = 1``), x [B, L, Cin] -> y [B, L * stride + row_off, Cout]; ``pc`` from ``pack_conv_transpose``.
+    One launch of the dedicated kernel (``mi355_upsample_polyphase``) where ``upsample_polyphase_eligible``; every other call runs the polyphase
+    ``conv_gemm`` (and the row copy) it stands for (the kernel is bit-equal to that launch on the wave-specialised conv kernel)."""
+    B, L, _, xbs, ldx = _nlc(x)
+    u = stride
+    cout = pc.cout // u
+    kfull = pc.k * u
+    p = (kfull - u) // 2
+    Lo = L * u + row_off
+    assert y.shape[0] == B and y.shape[1] >= Lo and y.shape[2] == cout and res.shape[0] == B and res.shape[1] >= Lo and res.shape[2] == cout
+    if upsample_polyphase_eligible(pc, u, pre_act=pre_act, precision=precision, res=res, pre_fq=pre_fq) and row_off in (0, 1):
+        _, _, _, rbs, ldr = _nlc(res)
+        _, _, _, ybs, ldy = _nlc(y)
+        assert pc.w.numel() >= _lib.load().mi355_packed_conv_weight_elems(pc.cout, pc.k, pc.cin)
+        if PROFILE is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            PROFILE.append((((L + 1) * B) if lens is None else (lens + 1).sum(), pc.cin, pc.cout, pc.k, 1, 1, e0, e1))
+        _lib.call_struct("mi355_upsample_polyphase", "mi355_upsample_polyphase_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, Cin=pc.cin, L=L,
+                         lens=_ptr(lens), B=B, w=_ptr(pc.w), bias=_ptr(pc.bias), Cout=cout, K=kfull, u=u, p=p, row_off=row_off, slope=pre_slope,
+                         precision=precision, res=_ptr(res), res_bstride=rbs, ldr=ldr, y=_ptr(y), y_bstride=ybs, ldy=ldy)
+        if PROFILE is not None:
+            e1.record()
+        return y
+    kp = pc.k
+    conv_gemm(x, pc, y, pad=kp - 1, lout=L + kp - 1, lens_in=lens, lens_out=None if lens is None else lens + (kp - 1), pre_act=pre_act,
+              pre_slope=pre_slope, res=res, precision=precision, pre_fq=pre_fq,
+              up=dict(s=u, p=p, cout=cout, row_off=row_off, lout=L * u, lens=None if lens is None else lens * u))
+    if row_off:
+        y[:, :row_off, :].copy_(res[:, :row_off, :])
+    return y
+
+
 # --------------------------------------------------------------------------------------- generic dsp
 def stft_frames(x: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, pad_mode: int, n_frames: int):
     """x [B, L] -> complex64 [B, n_frames, n_fft//2+1]."""

@@ -821,10 +821,15 @@ class KokoroEngine:
             xu = self._new(B, Lo, cout)
             lens_gemm = (lens_x + (kp - 1)) if ragged else None
             lens_ct = (lens_x * u) if ragged else None
-            self._convq(f"{g_n}.ups.{i}", x, self.ups[i], xu, pad=kp - 1, lout=L + kp - 1, lens_in=lens_x, lens_out=lens_gemm, pre_act=ACT_LEAKY,
-                        pre_slope=0.1, res=xsrc, up=dict(s=u, p=(k - u) // 2, cout=cout, row_off=1 if last else 0, lout=L * u, lens=lens_ct))
-            if last:
-                xu[:, 0, :].copy_(xsrc[:, 0, :])  # the zero left-pad row of "reflection_pad" + x_source
+            if not (self.qmods and self._isq(f"{g_n}.ups.{i}")) and ops.upsample_polyphase_eligible(self.ups[i], u, precision=self._prec(self.ups[i])):
+                # the dedicated kernel (decided by the weight image and the geometry, never by B or L): window converted once per row block, the
+                # pad row of the last stage written in the same launch; bit-equal to the general launch below on the wave-specialised kernel
+                ops.upsample_polyphase(x, self.ups[i], xsrc, xu, u, row_off=1 if last else 0, lens=lens_x, pre_slope=0.1, precision=self._prec(self.ups[i]))
+            else:
+                self._convq(f"{g_n}.ups.{i}", x, self.ups[i], xu, pad=kp - 1, lout=L + kp - 1, lens_in=lens_x, lens_out=lens_gemm, pre_act=ACT_LEAKY,
+                            pre_slope=0.1, res=xsrc, up=dict(s=u, p=(k - u) // 2, cout=cout, row_off=1 if last else 0, lout=L * u, lens=lens_ct))
+                if last:
+                    xu[:, 0, :].copy_(xsrc[:, 0, :])  # the zero left-pad row of "reflection_pad" + x_source
             if return_intermediates:
                 trace[f"xu{i}"] = xu.clone()
             acc = self._new(B, Lo, cout)
