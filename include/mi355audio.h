@@ -919,7 +919,7 @@ typedef struct {
   float* y2; int32_t ldy2; int32_t split;
   /* MI355_W_FP8 only: per-output-row dequantisation scale [N] (required): acc[n] * wscale[n] precedes the bias */
   const float* wscale;
-  int32_t norm_two_reads;  /* set by the library (MI355_GEMV_TWO_READS): compute the fused-norm statistics from a separate read of x; callers leave 0 */
+  int32_t reserved_norm_flag;  /* ignored; callers leave it 0 (kept so the layout of ABI 37 holds) */
   /* optional fused rotary embedding on the first rope_cols output columns (the q | k part of a fused q|k|v projection), interleaved pairs
      (2i, 2i + 1) inside heads of rope_dh channels -- nn.RoPE(traditional=True) / sesame/attention.py:41-105 at ONE position: rope_cos / rope_sin
      point at that position's table row [rope_dh / 2].  Plain epilogue only (no activation / colscale / residual / glu); 1..4 rows. */
@@ -928,10 +928,7 @@ typedef struct {
      embedding lookup fused into the projection that consumes it (sesame.py:392-396: embed the code just sampled, project it to the decoder width);
      the id is read on the device, so the sampler's output feeds the next GEMV without a host round trip or a separate gather launch */
   const int32_t* x_ids; int32_t x_id_offset;
-  /* optional scratch for splitting K over workgroups (5..8 rows, K > 2048, no fused norm: the down projections): split_ws holds
-     ceil(N / 16) * ceil(K / 2048) * 256 floats, split_cnt ceil(N / 16) int32 tickets (zero before the first call, left zero by every call).  Null =
-     the single-workgroup-per-column-group kernels. */
-  float* split_ws; int32_t* split_cnt;
+  float* reserved_ws; int32_t* reserved_cnt;   /* ignored; callers leave them null (kept so the layout of ABI 37 holds) */
   int32_t y2_dtype;   /* element type of y2: MI355_KV_F32 (0) / MI355_KV_BF16 / MI355_KV_F16 -- a 16-bit KV-cache slot (the reference's cache dtype);
                          y2 is then a uint16_t* in disguise and ldy2 counts 16-bit elements */
   int32_t w_policy;   /* cache policy of the weight stream (one-row kernels): 0 = default loads, 1 = non-temporal (`nt`): images that are streamed once
@@ -1087,7 +1084,7 @@ typedef struct {
                               RoPE positions count from it */
   const mi355_layer_desc* layers;                           /* HOST array of n_layers records */
   float* attn_split_ws; int32_t* attn_split_cnt;            /* nullable: workspace of mi355_flash_attn_args.split_* for B <= 8, Tq = 1 */
-  float* gemv_split_ws; int32_t* gemv_split_cnt;            /* nullable: mi355_gemv_args.split_ws / split_cnt sized for the largest projection of the stack */
+  float* reserved_gemv_ws; int32_t* reserved_gemv_cnt;      /* ignored; callers leave them null (kept so the layout of ABI 37 holds) */
   const float* final_norm_w; const float* final_norm_b;     /* nullable */
   int32_t kv_dtype;        /* MI355_KV_F32 / MI355_KV_BF16 / MI355_KV_F16: element type of every layer's kv buffer (the reference keeps its caches in the
                               checkpoint dtype, lm/models/cache.py:104-176).  16-bit caches need the stores that exist: q|k|v GEMV with the rotary pairs in its

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const mi355_gemv_args
         const double var = ss / K - mean * mean;
         const float vf = (float)(var > 0.0 ? var : 0.0);
         st_mean[m] = (float)mean;
-        st_rstd[m] = a.norm == 1 ? 1.0f / sqrtf(vf + a.norm_eps) : rsqrtf(vf + a.norm_eps);
+        st_rstd[m] = norm_rstd(a.norm, vf, a.norm_eps);
       }
     }
     __syncthreads();

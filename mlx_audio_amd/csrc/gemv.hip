@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include "linear_common.h"
 
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(256, (MT >= 8 && NC == 2 && WT != MI355_W_FP8) ? 3 
   // single = the whole row fits one staged chunk: the statistics are then computed from the LDS copy inside the staging step -- ONE L2 round
   // trip for x instead of three (two dependent row reads per wave for the statistics at 8 rows, then the staging read).  Decode-step
   // launches are bound by exactly this dependent chain, not by bytes (profiles/r1_decode_runner_ab_call21.txt).
-  const bool single = a.norm && a.K <= KC && !a.norm_two_reads;
+  const bool single = a.norm && a.K <= KC;
   if (a.norm && !single) {
     // both rows of this wave are in flight before the first reduction (rows m and m + 4: one round trip, not two)
     const int m0 = wave, m1 = wave + 4;
@@ -192,22 +193,10 @@ __global__ __launch_bounds__(256, (MT >= 8 && NC == 2 && WT != MI355_W_FP8) ? 3 
           }
         }
         const float var = wave_sum(q) / (float)a.K;
-        if (lane == 0) { st_mean[m] = mean; st_rstd[m] = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps); }
+        if (lane == 0) { st_mean[m] = mean; st_rstd[m] = norm_rstd(a.norm, var, a.norm_eps); }
       }
     } else {
-      for (int m = wave; m < a.M; m += 4) {
-        const float* xr = a.x + (int64_t)m * a.ldx;
-        float s = 0.f, q = 0.f;
-        for (int k = lane * 4; k < a.K; k += 256) { const float4 t = *(const float4*)(xr + k); s += (t.x + t.y) + (t.z + t.w); }
-        const float mean = a.norm == 1 ? wave_sum(s) / (float)a.K : 0.f;
-        for (int k = lane * 4; k < a.K; k += 256) {
-          const float4 t = *(const float4*)(xr + k);
-          const float d0 = t.x - mean, d1 = t.y - mean, d2 = t.z - mean, d3 = t.w - mean;
-          q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        }
-        const float var = wave_sum(q) / (float)a.K;
-        if (lane == 0) { st_mean[m] = mean; st_rstd[m] = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps); }
-      }
+      for (int m = wave; m < a.M; m += 4) norm_row_stats(a.x + (int64_t)m * a.ldx, a.K, lane, a.norm, a.norm_eps, st_mean, st_rstd, m);
     }
   }
   for (int base = 0; base < n_it; base += D) {
@@ -246,19 +235,7 @@ __global__ __launch_bounds__(256, (MT >= 8 && NC == 2 && WT != MI355_W_FP8) ? 3 
               }
             }
             __syncthreads();
-            for (int m = wave; m < a.M; m += 4) {
-              const float* xr = xs + m * KC;
-              float s = 0.f, q = 0.f;
-              for (int k = lane * 4; k < a.K; k += 256) { const float4 t = *(const float4*)(xr + k); s += (t.x + t.y) + (t.z + t.w); }
-              const float mean = a.norm == 1 ? wave_sum(s) / (float)a.K : 0.f;
-              for (int k = lane * 4; k < a.K; k += 256) {
-                const float4 t = *(const float4*)(xr + k);
-                const float d0 = t.x - mean, d1 = t.y - mean, d2 = t.z - mean, d3 = t.w - mean;
-                q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-              }
-              const float var = wave_sum(q) / (float)a.K;
-              if (lane == 0) { st_mean[m] = mean; st_rstd[m] = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps); }
-            }
+            for (int m = wave; m < a.M; m += 4) norm_row_stats(xs + m * KC, a.K, lane, a.norm, a.norm_eps, st_mean, st_rstd, m);
             __syncthreads();
           }
 #pragma unroll
@@ -282,9 +259,6 @@ __global__ __launch_bounds__(256, (MT >= 8 && NC == 2 && WT != MI355_W_FP8) ? 3 
       }
       const int kl = (it % IPC) * SL + lane * EPL;  // position inside the staged chunk
       if (it * SL + lane * EPL < a.K) {
-        float wf[NC][EPL];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) cvt_w16<WT>(ring[d][c], wf[c]);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
           float xv[EPL];
@@ -293,10 +267,7 @@ __global__ __launch_bounds__(256, (MT >= 8 && NC == 2 && WT != MI355_W_FP8) ? 3 
             const float4 t = *(const float4*)(xs + m * KC + kl + 4 * j4);
             xv[4 * j4] = t.x; xv[4 * j4 + 1] = t.y; xv[4 * j4 + 2] = t.z; xv[4 * j4 + 3] = t.w;
           }
-#pragma unroll
-          for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int j = 0; j < EPL; ++j) acc[c][m] = fmaf(xv[j], wf[c][j], acc[c][m]);
+          gemv_slice_fma<WT, NC, MT>(ring[d], xv, acc, m);   // (the conversion of the weight pieces is the same for every row: done once after inlining)
         }
       }
       if (it + D < n_it) issue(it + D, ring[d]);
@@ -306,117 +277,20 @@ __global__ __launch_bounds__(256, (MT >= 8 && NC == 2 && WT != MI355_W_FP8) ? 3 
   gemv_finish<MT, NC>(a, acc, n0, lane);
 }
 
-// Resident-x variant for 4..8 input rows: at M = 8 the staging of x (M * K * 4 bytes per workgroup) costs more L2 traffic than the weight
-// rows a 4-wave workgroup consumes, so the rows are staged ONCE per workgroup (dynamic LDS, the fused norm applied on the way in) and the
-// waves then walk many column groups (grid-stride) with no barrier inside the loop -- only the weight stream touches memory.
-template <int MT, int NC, int WT>
-__global__ __launch_bounds__(256) void gemv_res_kernel(const mi355_gemv_args a, const int ngroups) {
-  constexpr int EPL = mi355_wt<WT>::EPL, ESZ = 16 / EPL, SL = 64 * EPL;
-  constexpr int D = 4;
-  extern __shared__ __attribute__((aligned(16))) float xr_s[];  // [MT][K]
-  __shared__ float st_mean[8], st_rstd[8];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = a.K;
-  if (a.norm) {
-    for (int m = wave; m < a.M; m += 4) {
-      const float* xr = a.x + (int64_t)m * a.ldx;
-      float s = 0.f;
-      for (int k = lane * 4; k < K; k += 256) { const float4 t = *(const float4*)(xr + k); s += (t.x + t.y) + (t.z + t.w); }
-      const float mean = a.norm == 1 ? wave_sum(s) / (float)K : 0.f;
-      float q = 0.f;
-      for (int k = lane * 4; k < K; k += 256) {
-        const float4 t = *(const float4*)(xr + k);
-        const float d0 = t.x - mean, d1 = t.y - mean, d2 = t.z - mean, d3 = t.w - mean;
-        q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-      }
-      const float var = wave_sum(q) / (float)K;
-      if (lane == 0) { st_mean[m] = mean; st_rstd[m] = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps); }
-    }
-    __syncthreads();
-  }
-  for (int e = tid * 4; e < MT * K; e += 1024) {
-    const int m = e / K, k = e - m * K;
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (m < a.M) {
-      t = *(const float4*)(a.x + (int64_t)m * a.ldx + k);
-      if (a.norm) {
-        const float mu = st_mean[m], rs = st_rstd[m];
-        float4 w4 = make_float4(1.f, 1.f, 1.f, 1.f), b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (a.norm_weight) w4 = *(const float4*)(a.norm_weight + k);
-        if (a.norm_bias) b4 = *(const float4*)(a.norm_bias + k);
-        t = make_float4((t.x - mu) * rs * w4.x + b4.x, (t.y - mu) * rs * w4.y + b4.y, (t.z - mu) * rs * w4.z + b4.z, (t.w - mu) * rs * w4.w + b4.w);
-      }
-    }
-    *(float4*)(xr_s + e) = t;
-  }
-  __syncthreads();
-  const int n_it = (K + SL - 1) / SL;
-  for (int g = blockIdx.x * 4 + wave; g < ngroups; g += gridDim.x * 4) {
-    const int n0 = g * NC;
-    float acc[NC][MT];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int m = 0; m < MT; ++m) acc[c][m] = 0.f;
-    const uint8_t* wrow[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int n = n0 + c < a.N ? n0 + c : a.N - 1;
-      wrow[c] = (const uint8_t*)a.w + (int64_t)n * a.ldw * ESZ;
-    }
-    uint4 ring[D][NC];
-    auto issue = [&](int it, uint4 (&dst)[NC]) {
-      const int k = it * SL + lane * EPL;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) dst[c] = k < K ? *(const uint4*)(wrow[c] + (int64_t)k * ESZ) : make_uint4(0u, 0u, 0u, 0u);
-    };
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-      if (d < n_it) issue(d, ring[d]);
-    for (int base = 0; base < n_it; base += D) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        const int it = base + d;
-        if (it >= n_it) break;
-        const int k = it * SL + lane * EPL;
-        if (k < K) {
-          float wf[NC][EPL];
-#pragma unroll
-          for (int c = 0; c < NC; ++c) cvt_w16<WT>(ring[d][c], wf[c]);
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            float xv[EPL];
-#pragma unroll
-            for (int j4 = 0; j4 < EPL / 4; ++j4) {
-              const float4 t = *(const float4*)(xr_s + m * K + k + 4 * j4);
-              xv[4 * j4] = t.x; xv[4 * j4 + 1] = t.y; xv[4 * j4 + 2] = t.z; xv[4 * j4 + 3] = t.w;
-            }
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-#pragma unroll
-              for (int j = 0; j < EPL; ++j) acc[c][m] = fmaf(xv[j], wf[c][j], acc[c][m]);
-          }
-        }
-        if (it + D < n_it) issue(it + D, ring[d]);
-      }
-    }
-    gemv_finish<MT, NC>(a, acc, n0, lane);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------- one input row (M = 1)
 // The single-sequence decode step (CSM generate_frame: 16 backbone + 31 x 4 depth-decoder layer steps per frame, sesame.py:361-404) is a chain
 // of ~650 of these per frame; profiles/r2_kernel_stats_csm_bygrid_call10.txt has the chunked kernel above at 5.8 us (q|k|v, 3 MB), 14.2 us
 // (gate|up, 34-67 MB) and 6.7 us (o-proj / down) per launch -- bound by what happens around the weight stream: every 8-column workgroup
 // re-stages x through LDS behind three barriers and recomputes the norm statistics, and a wave's life is two k-slices long.
 //
-// gemv1_res_kernel (K <= 4 slices, i.e. 2048 elements at 16 bits): a wave is autonomous.  Lane l multiplies the weights at k = it * SL + l * EPL
+// gemv1_stream_kernel (K <= 2048, i.e. 4 slices at 16 bits): a wave is autonomous.  Lane l multiplies the weights at k = it * SL + l * EPL
 // with the x values at the same k -- ITS OWN 8 (16) floats of each slice -- so x lives in registers, the fused RMSNorm / LayerNorm statistics are
-// one in-register pass plus a wave reduction, and there is no LDS and no barrier anywhere.  Waves walk column groups grid-stride with the next
-// group's weights already in flight (double buffer), so the stream does not stop at group boundaries.
+// one in-register pass plus a wave reduction, and there is no LDS and no barrier anywhere.  A wave walks a contiguous run of column groups with
+// the next two groups' weights already in flight (two buffers), so the stream does not stop at group boundaries.
 //
 // gemv1_splitk_kernel (K > 2048: the down projections): 4 columns per workgroup, the 4 waves split K; a lane streams its slices of x with the
 // weights (same prefetch ring), partial sums meet in LDS once.  16 KB of weights in flight per wave keeps HBM busy with only N / 4 workgroups.
+
 // 16 bytes of the weight stream under the launch's cache policy (NT: global_load_dwordx4 ... nt)
 template <bool NT>
 __device__ __forceinline__ uint4 ldw16(const void* p) {
@@ -429,122 +303,16 @@ __device__ __forceinline__ uint4 ldw16(const void* p) {
   }
 }
 
-// HALF: K <= 1024 (half the slices: half the weight ring and x registers -- the 1024-wide depth decoder / code predictor then keep 4 waves per SIMD
-// resident instead of 2, see launch_gemv1)
-template <int NC, int WT, bool NT = false, bool HALF = false>
-__global__ __launch_bounds__(256) void gemv1_res_kernel(const mi355_gemv_args a, const int ngroups) {
-  constexpr int EPL = mi355_wt<WT>::EPL, ESZ = 16 / EPL, SL = 64 * EPL;
-  constexpr int NIT = 2048 / (64 * 8) / (EPL / 8) / (HALF ? 2 : 1);  // slices covering K <= 2048 (4 at 16 bits, 2 for fp8 whose slice is 1024 elements)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int K = a.K;
-  const float* xrow = a.x_ids ? a.x + ((int64_t)a.x_ids[0] + a.x_id_offset) * a.ldx : a.x;   // optional fused embedding lookup
-  float xr[NIT][EPL];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int k = it * SL + lane * EPL;
-#pragma unroll
-    for (int j4 = 0; j4 < EPL / 4; ++j4) {
-      const float4 t = k < K ? *(const float4*)(xrow + k + 4 * j4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      xr[it][4 * j4] = t.x; xr[it][4 * j4 + 1] = t.y; xr[it][4 * j4 + 2] = t.z; xr[it][4 * j4 + 3] = t.w;
-    }
-  }
-  uint4 ring[2][NIT][NC];
-  auto issue = [&](int g, uint4 (&dst)[NIT][NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int n = g * NC + c < a.N ? g * NC + c : a.N - 1;  // clamp: tail columns recompute the last row, never stored
-      const uint8_t* wrow = (const uint8_t*)a.w + (int64_t)n * a.ldw * ESZ;
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int k = it * SL + lane * EPL;
-        dst[it][c] = k < K ? ldw16<NT>(wrow + (int64_t)k * ESZ) : make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
-  };
-  int g = blockIdx.x * 4 + wave;
-  const int gstep = gridDim.x * 4;
-  if (g < ngroups) issue(g, ring[0]);   // the weight stream starts before the statistics: its HBM latency overlaps the norm
-  // the norm weights are requested before the statistics too (one L2 round trip less on the kernel's dependent chain)
-  float4 nwq[NIT][EPL / 4];
-  if (a.norm) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int k = it * SL + lane * EPL;
-#pragma unroll
-      for (int j4 = 0; j4 < EPL / 4; ++j4)
-        nwq[it][j4] = (a.norm_weight && k < K) ? *(const float4*)(a.norm_weight + k + 4 * j4) : make_float4(1.f, 1.f, 1.f, 1.f);
-    }
-  }
-  if (a.norm) {
-    float mean = 0.f;
-    if (a.norm == 1) {
-      float s = 0.f;
-#pragma unroll
-      for (int it = 0; it < NIT; ++it)
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) s += xr[it][j];
-      mean = wave_sum_fast(s) / (float)K;
-    }
-    float q = 0.f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it)
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) {
-        const float d = (it * SL + lane * EPL + j < K) ? xr[it][j] - mean : 0.f;
-        q += d * d;
-      }
-    const float var = wave_sum_fast(q) / (float)K;
-    const float rstd = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int k = it * SL + lane * EPL;
-      if (k < K) {
-#pragma unroll
-        for (int j4 = 0; j4 < EPL / 4; ++j4) {
-          const float4 w4 = nwq[it][j4];
-          const float4 b4 = a.norm_bias ? *(const float4*)(a.norm_bias + k + 4 * j4) : make_float4(0.f, 0.f, 0.f, 0.f);
-          xr[it][4 * j4] = (xr[it][4 * j4] - mean) * rstd * w4.x + b4.x;
-          xr[it][4 * j4 + 1] = (xr[it][4 * j4 + 1] - mean) * rstd * w4.y + b4.y;
-          xr[it][4 * j4 + 2] = (xr[it][4 * j4 + 2] - mean) * rstd * w4.z + b4.z;
-          xr[it][4 * j4 + 3] = (xr[it][4 * j4 + 3] - mean) * rstd * w4.w + b4.w;
-        }
-      }
-    }
-  }
-  int buf = 0;
-  for (; g < ngroups; g += gstep, buf ^= 1) {
-    if (g + gstep < ngroups) {
-      if (buf == 0) issue(g + gstep, ring[1]); else issue(g + gstep, ring[0]);
-    }
-    float acc[NC][1];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c][0] = 0.f;
-    auto consume = [&](uint4 (&src)[NIT][NC]) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          float wf[EPL];
-          cvt_w16<WT>(src[it][c], wf);
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) acc[c][0] = fmaf(xr[it][j], wf[j], acc[c][0]);
-        }
-      }
-    };
-    if (buf == 0) consume(ring[0]); else consume(ring[1]);
-    gemv_finish<1, NC>(a, acc, g * NC, lane);
-  }
-}
-
-
-// gemv1_stream_kernel: gemv1_res_kernel's arithmetic with a memory schedule that has ONE dependent round trip.  The old loop's loads sat under
-// `k < K` / `g + gstep < ngroups` branches; at every control-flow join the compiler's wait-count pass has to assume the path with the fewest
-// younger loads, so each group's data was awaited with s_waitcnt vmcnt(0) -- the prefetched NEXT group included -- and every group then paid its
-// own epilogue round trip (bias / residual loads -> store) in lane 0: ~3.5 us per 8 KB group and wave, whatever the bandwidth.  Here
+// gemv1_stream_kernel: its memory schedule has ONE dependent round trip.  Loads under `k < K` / `g + gstep < ngroups` branches (the form
+// gemv1_attn_kernel below still has) cost a wait each: at every control-flow join the compiler's wait-count pass has to assume the path with the
+// fewest younger loads, so each group's data is awaited with s_waitcnt vmcnt(0) -- the prefetched NEXT group included -- and an epilogue per group
+// pays its own round trip (bias / residual loads -> store) in lane 0: ~3.5 us per 8 KB group and wave, whatever the bandwidth.  Here
 //  * every load is unconditional (out-of-range k / groups are clamped to a valid address, x is zeroed instead): the loop body is straight-line
 //    code and the waits are exact (vmcnt = the loads of the younger group);
 //  * a wave owns a CONTIGUOUS run of <= 64 groups and parks group i's finished sums in lane i; after the last group the lanes run the
 //    epilogue side by side: its loads and stores are coalesced over the run and are awaited once per wave, not once per group.
+// HALF: K <= 1024 (half the slices: half the weight ring and x registers -- the 1024-wide depth decoder / code predictor then keep 4 waves per SIMD
+// resident instead of 2, see launch_gemv1)
 template <int NC, int WT, bool NT, bool HALF>
 __global__ __launch_bounds__(256) void gemv1_stream_kernel(const mi355_gemv_args a, const int ngroups, const int gpw) {
   constexpr int EPL = mi355_wt<WT>::EPL, ESZ = 16 / EPL, SL = 64 * EPL;
@@ -619,7 +387,7 @@ __global__ __launch_bounds__(256) void gemv1_stream_kernel(const mi355_gemv_args
         q += d * d;
       }
     const float var = wave_sum_fast(q) / (float)K;
-    const float rstd = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps);
+    const float rstd = norm_rstd(a.norm, var, a.norm_eps);
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
 #pragma unroll
@@ -653,22 +421,14 @@ __global__ __launch_bounds__(256) void gemv1_stream_kernel(const mi355_gemv_args
 #pragma unroll
   for (int c = 0; c < NC; ++c) mine[c][0] = 0.f;
   auto consume = [&](uint4 (&src)[NIT][NC], int gi) {
-    float acc[NC];
+    float acc[NC][1];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.f;
+    for (int c = 0; c < NC; ++c) acc[c][0] = 0.f;
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        float wf[EPL];
-        cvt_w16<WT>(src[it][c], wf);
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) acc[c] = fmaf(xr[it][j], wf[j], acc[c]);
-      }
-    }
+    for (int it = 0; it < NIT; ++it) gemv_slice_fma<WT, NC, 1>(src[it], xr[it], acc, 0);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      const float t = wave_sum_fast(acc[c]);
+      const float t = wave_sum_fast(acc[c][0]);
       mine[c][0] = lane == gi ? t : mine[c][0];
     }
   };
@@ -690,8 +450,9 @@ __global__ __launch_bounds__(256) void gemv1_stream_kernel(const mi355_gemv_args
 
 // gemv1_attn_kernel: the o-proj of a decode step with the attention of that step as its PROLOGUE (M == 1, K = heads * dh <= 2048, at most 64 cached
 // positions: the depth decoder of CSM attends over <= 32 positions, 124 times per frame).  Every workgroup recomputes the whole attention row -- a
-// few thousand multiply-adds on K | V rows that sit in L2 -- while its slice of the weight stream is already in flight, and then runs the
-// register-resident GEMV of gemv1_res_kernel on it: one launch per layer less, and the scores never touch memory.  x = the (rotated) query row.
+// few thousand multiply-adds on K | V rows that sit in L2 -- while its slice of the weight stream is already in flight, and then runs a
+// register-resident GEMV on it (x in registers as in gemv1_stream_kernel; one column per wave, grid-stride, guarded loads and a double buffer, the
+// epilogue per column in lane 0): one launch per layer less, and the scores never touch memory.  x = the (rotated) query row.
 template <int WT, bool NT>
 __global__ __launch_bounds__(256) void gemv1_attn_kernel(const mi355_gemv_args a, const int ngroups) {
   constexpr int NC = 1;
@@ -814,90 +575,17 @@ __global__ __launch_bounds__(256) void gemv1_attn_kernel(const mi355_gemv_args a
     acc[0][0] = 0.f;
     auto consume = [&](uint4 (&src)[NIT][NC]) {
 #pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        float wf[EPL];
-        cvt_w16<WT>(src[it][0], wf);
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) acc[0][0] = fmaf(xr[it][j], wf[j], acc[0][0]);
-      }
+      for (int it = 0; it < NIT; ++it) gemv_slice_fma<WT, NC, 1>(src[it], xr[it], acc, 0);
     };
     if (buf == 0) consume(ring[0]); else consume(ring[1]);
     gemv_finish<1, NC>(a, acc, g, lane);
   }
 }
 
-template <int WT, bool NT = false>
-__global__ __launch_bounds__(256) void gemv1_splitk_old_kernel(const mi355_gemv_args a) {
-  constexpr int NC = 4, D = 4;
-  constexpr int EPL = mi355_wt<WT>::EPL, ESZ = 16 / EPL, SL = 64 * EPL;
-  __shared__ float part[4][NC];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n0 = blockIdx.x * NC;
-  const int n_it = (a.K + SL - 1) / SL;
-  const int per = (n_it + 3) / 4;                       // slices per wave
-  const int it0 = wave * per, it1 = it0 + per < n_it ? it0 + per : n_it;
-  const uint8_t* wrow[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int n = n0 + c < a.N ? n0 + c : a.N - 1;
-    wrow[c] = (const uint8_t*)a.w + (int64_t)n * a.ldw * ESZ;
-  }
-  const float* xrow = a.x_ids ? a.x + ((int64_t)a.x_ids[0] + a.x_id_offset) * a.ldx : a.x;
-  uint4 wring[D][NC];
-  float4 xring[D][EPL / 4];
-  auto issue = [&](int it, int d) {
-    const int k = it * SL + lane * EPL;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) wring[d][c] = k < a.K ? ldw16<NT>(wrow[c] + (int64_t)k * ESZ) : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int j4 = 0; j4 < EPL / 4; ++j4) xring[d][j4] = k < a.K ? *(const float4*)(xrow + k + 4 * j4) : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-    if (it0 + d < it1) issue(it0 + d, d);
-  float acc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = 0.f;
-  for (int base = it0; base < it1; base += D) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const int it = base + d;
-      if (it >= it1) break;
-      float xv[EPL];
-#pragma unroll
-      for (int j4 = 0; j4 < EPL / 4; ++j4) {
-        xv[4 * j4] = xring[d][j4].x; xv[4 * j4 + 1] = xring[d][j4].y; xv[4 * j4 + 2] = xring[d][j4].z; xv[4 * j4 + 3] = xring[d][j4].w;
-      }
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        float wf[EPL];
-        cvt_w16<WT>(wring[d][c], wf);
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) acc[c] = fmaf(xv[j], wf[j], acc[c]);
-      }
-      if (it + D < it1) issue(it + D, d);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = wave_sum_fast(acc[c]);
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) part[wave][c] = acc[c];
-  }
-  __syncthreads();
-  const int c = threadIdx.x;
-  if (c < NC && n0 + c < a.N) {
-    const int n = n0 + c;
-    const float sum = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];   // fixed order: run-to-run identical
-    const float ws = a.wscale ? a.wscale[n] * kFp8Unbias : 1.f;
-    linear_finish(a, 0, n, sum * ws);
-  }
-}
-
-// gemv1_splitk_kernel, second form: the first one's `k < K ? load : 0` guards compiled to a branch per load, several of them with their own
-// s_waitcnt vmcnt(0) -- up to eight SERIAL HBM round trips before the first multiply (7.0-8.7 us for the 16.8 MB down projection of the CSM depth
-// decoder, whose bytes are 2.7 us at the chip's rate).  Here every load is unconditional (clamped address, x zeroed instead), the epilogue's
-// operands are requested first, and the slice loop is straight-line code: one round trip.
+// gemv1_splitk_kernel: `k < K ? load : 0` guards compile to a branch per load, several of them with their own s_waitcnt vmcnt(0) -- up to eight
+// SERIAL HBM round trips before the first multiply (7.0-8.7 us for the 16.8 MB down projection of the CSM depth decoder, whose bytes are 2.7 us
+// at the chip's rate).  So every load is unconditional (clamped address, x zeroed instead), the epilogue's operands are requested first, and the
+// slice loop is straight-line code: one round trip.
 template <int WT, bool NT = false>
 __global__ __launch_bounds__(256) void gemv1_splitk_kernel(const mi355_gemv_args a) {
   constexpr int NC = 4, D = 4;
@@ -936,9 +624,9 @@ __global__ __launch_bounds__(256) void gemv1_splitk_kernel(const mi355_gemv_args
   };
 #pragma unroll
   for (int d = 0; d < D; ++d) issue(it0 + d, d);
-  float acc[NC];
+  float acc[NC][1];
 #pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = 0.f;
+  for (int c = 0; c < NC; ++c) acc[c][0] = 0.f;
   auto consume = [&](int d) {
     float xv[EPL];
 #pragma unroll
@@ -946,13 +634,7 @@ __global__ __launch_bounds__(256) void gemv1_splitk_kernel(const mi355_gemv_args
       xv[4 * j4] = okring[d] ? xring[d][j4].x : 0.f; xv[4 * j4 + 1] = okring[d] ? xring[d][j4].y : 0.f;
       xv[4 * j4 + 2] = okring[d] ? xring[d][j4].z : 0.f; xv[4 * j4 + 3] = okring[d] ? xring[d][j4].w : 0.f;
     }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      float wf[EPL];
-      cvt_w16<WT>(wring[d][c], wf);
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) acc[c] = fmaf(xv[j], wf[j], acc[c]);
-    }
+    gemv_slice_fma<WT, NC, 1>(wring[d], xv, acc, 0);
   };
   int base = it0;
   for (; base + D < it1; base += D) {
@@ -965,10 +647,10 @@ __global__ __launch_bounds__(256) void gemv1_splitk_kernel(const mi355_gemv_args
 #pragma unroll
   for (int d = 0; d < D; ++d) consume(d);               // the last block: nothing left to request
 #pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = wave_sum_fast(acc[c]);
+  for (int c = 0; c < NC; ++c) acc[c][0] = wave_sum_fast(acc[c][0]);
   if (lane == 0) {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) part[wave][c] = acc[c];
+    for (int c = 0; c < NC; ++c) part[wave][c] = acc[c][0];
   }
   __syncthreads();
   if (ec >= 0) {
@@ -981,81 +663,52 @@ __global__ __launch_bounds__(256) void gemv1_splitk_kernel(const mi355_gemv_args
   }
 }
 
+// the launch's cache policy for the weight stream: mi355_gemv_args.w_policy, or MI355_GEMV_NT = 0 / 1 for every launch (A/B knob)
+bool weights_nontemporal(const mi355_gemv_args& a) {
+  static const int nt_env = getenv("MI355_GEMV_NT") ? atoi(getenv("MI355_GEMV_NT")) : -1;
+  return nt_env >= 0 ? nt_env != 0 : a.w_policy == 1;
+}
+
+// a run-time flag as a compile-time one: f(std::true_type / std::false_type)
+template <class F>
+void with_flag(const bool flag, F&& f) {
+  if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+
 template <int WT>
 int launch_gemv1(const mi355_gemv_args& a, hipStream_t st) {
-  constexpr int EPL = mi355_wt<WT>::EPL;
-  const int kres = 2048 * (EPL / 8) / (EPL / 8);  // K the register-resident kernel covers (2048 elements for every weight type)
+  const int kres = 2048;  // K the register-resident kernels cover (2048 elements for every weight type)
   MI355_CLEAR_ERROR();
   if (a.attn_k) {   // attention prologue: validated by mi355_gemv
     int blocks = (a.N + 3) / 4;
     if (blocks > 1024) blocks = 1024;
-    static const int nt_env0 = getenv("MI355_GEMV_NT") ? atoi(getenv("MI355_GEMV_NT")) : -1;
-    if (nt_env0 >= 0 ? nt_env0 != 0 : a.w_policy == 1) hipLaunchKernelGGL((gemv1_attn_kernel<WT, true>), dim3(blocks), dim3(256), 0, st, a, a.N);
-    else hipLaunchKernelGGL((gemv1_attn_kernel<WT, false>), dim3(blocks), dim3(256), 0, st, a, a.N);
+    with_flag(weights_nontemporal(a), [&](auto nt) { hipLaunchKernelGGL((gemv1_attn_kernel<WT, decltype(nt)::value>), dim3(blocks), dim3(256), 0, st, a, a.N); });
     MI355_LAUNCH_CHECK("gemv(M=1, attention prologue)");
     return MI355_OK;
   }
   if (a.K <= kres) {
     const bool two = a.glu || a.rope_cos || a.N >= 4096;
     const int ngroups = two ? (a.N + 1) / 2 : a.N;
-    static const int nt_env = getenv("MI355_GEMV_NT") ? atoi(getenv("MI355_GEMV_NT")) : -1;   // A/B knob: 0 / 1 overrides every launch's policy
-    const bool nt = nt_env >= 0 ? nt_env != 0 : a.w_policy == 1;
-    const bool half = a.K <= 1024;
     // ONE resident round: the grid is what the chip holds at this instantiation's register count (the two-column kernel at K = 2048 takes 224
     // registers = 2 workgroups per CU; launched as 1024 workgroups it ran two full rounds, each with its own x load -> statistics -> first HBM
-    // round trip: 13.9 us for the 33.5 MB gate|up image of the depth decoder, profiles/r2_kernel_stats_csm_bygrid_call11_m1_kernels.txt); the rest
-    // of the columns come grid-stride with their weights prefetched
-    auto go = [&](auto kern) {
-      const int resident = resident_workgroups((const void*)kern);   // per kernel ADDRESS and device (see resident_workgroups)
-      int blocks = (ngroups + 3) / 4;
-      if (blocks > resident) blocks = resident;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, st, a, ngroups);
-    };
-    static const bool old1 = getenv("MI355_GEMV1_OLD") != nullptr && getenv("MI355_GEMV1_OLD")[0] == '1';   // A/B knob: the grid-stride kernel
+    // round trip: 13.9 us for the 33.5 MB gate|up image of the depth decoder, profiles/r2_kernel_stats_csm_bygrid_call11_m1_kernels.txt)
     auto gs = [&](auto kern) {
-      const int resident = resident_workgroups((const void*)kern);
+      const int resident = resident_workgroups((const void*)kern);   // per kernel ADDRESS and device (see resident_workgroups)
       // one resident round of waves, every wave the same contiguous run of groups (<= 64: one lane per group for the epilogue)
       int gpw = (ngroups + resident * 4 - 1) / (resident * 4);
       if (gpw > 64) gpw = 64;
       const int blocks = (ngroups + 4 * gpw - 1) / (4 * gpw);
       hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, st, a, ngroups, gpw);
     };
-    if (!old1) {
-      if (half) {
-        if (two && nt) gs(gemv1_stream_kernel<2, WT, true, true>);
-        else if (two) gs(gemv1_stream_kernel<2, WT, false, true>);
-        else if (nt) gs(gemv1_stream_kernel<1, WT, true, true>);
-        else gs(gemv1_stream_kernel<1, WT, false, true>);
-      } else {
-        if (two && nt) gs(gemv1_stream_kernel<2, WT, true, false>);
-        else if (two) gs(gemv1_stream_kernel<2, WT, false, false>);
-        else if (nt) gs(gemv1_stream_kernel<1, WT, true, false>);
-        else gs(gemv1_stream_kernel<1, WT, false, false>);
-      }
-      MI355_LAUNCH_CHECK("gemv(M=1, register-resident x, streamed groups)");
-      return MI355_OK;
-    }
-    if (half) {
-      if (two && nt) go(gemv1_res_kernel<2, WT, true, true>);
-      else if (two) go(gemv1_res_kernel<2, WT, false, true>);
-      else if (nt) go(gemv1_res_kernel<1, WT, true, true>);
-      else go(gemv1_res_kernel<1, WT, false, true>);
-    } else {
-      if (two && nt) go(gemv1_res_kernel<2, WT, true>);
-      else if (two) go(gemv1_res_kernel<2, WT>);
-      else if (nt) go(gemv1_res_kernel<1, WT, true>);
-      else go(gemv1_res_kernel<1, WT>);
-    }
-    MI355_LAUNCH_CHECK("gemv(M=1, register-resident x)");
+    with_flag(two, [&](auto c2) {
+      with_flag(weights_nontemporal(a), [&](auto nt) {
+        with_flag(a.K <= 1024, [&](auto half) { gs(gemv1_stream_kernel<decltype(c2)::value ? 2 : 1, WT, decltype(nt)::value, decltype(half)::value>); });
+      });
+    });
+    MI355_LAUNCH_CHECK("gemv(M=1, register-resident x, streamed groups)");
     return MI355_OK;
   }
-  static const int nt_env2 = getenv("MI355_GEMV_NT") ? atoi(getenv("MI355_GEMV_NT")) : -1;
-  static const bool old2 = getenv("MI355_GEMV1_OLD") != nullptr && getenv("MI355_GEMV1_OLD")[0] == '1';
-  const bool nt2 = nt_env2 >= 0 ? nt_env2 != 0 : a.w_policy == 1;
-  if (old2 && nt2) hipLaunchKernelGGL((gemv1_splitk_old_kernel<WT, true>), dim3((a.N + 3) / 4), dim3(256), 0, st, a);
-  else if (old2) hipLaunchKernelGGL((gemv1_splitk_old_kernel<WT>), dim3((a.N + 3) / 4), dim3(256), 0, st, a);
-  else if (nt2) hipLaunchKernelGGL((gemv1_splitk_kernel<WT, true>), dim3((a.N + 3) / 4), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((gemv1_splitk_kernel<WT>), dim3((a.N + 3) / 4), dim3(256), 0, st, a);
+  with_flag(weights_nontemporal(a), [&](auto nt) { hipLaunchKernelGGL((gemv1_splitk_kernel<WT, decltype(nt)::value>), dim3((a.N + 3) / 4), dim3(256), 0, st, a); });
   MI355_LAUNCH_CHECK("gemv(M=1, split K)");
   return MI355_OK;
 }
@@ -1063,32 +716,11 @@ int launch_gemv1(const mi355_gemv_args& a, hipStream_t st) {
 template <int MT, int WT>
 int launch_gemv(const mi355_gemv_args& a, hipStream_t st) {
   // one column per wave keeps the most wavefronts (and weight bytes) in flight; two columns per wave halve the LDS reads of x per weight
-  // byte, which is what binds at 8 rows (16 LDS bytes per weight byte at NC = 1) and for very wide outputs
-  static const int nc_env = getenv("MI355_GEMV_NC") ? atoi(getenv("MI355_GEMV_NC")) : 0;  // A/B knob (1 | 2); SwiGLU pairs always need 2
-  const int nc = (a.glu || a.rope_cos) ? 2 : (nc_env == 1 || nc_env == 2) ? nc_env : ((MT >= 8 || a.N >= 16384) ? 2 : 1);
-  if constexpr (MT >= 4) {
-    const size_t lds = (size_t)MT * a.K * sizeof(float);
-    // Measured (profiles/r1_kernel_stats_qwen3_1p7b_b8_v4_resident.txt): 22.0 us vs 18.9 us per launch for the chunked kernel at M = 8 -- these
-    // launches are bound by their dependent chain (statistics -> staging -> first weight slice), not by the re-staging of x, and the chunked
-    // kernel overlaps the weight latency with the staging.  Kept as an opt-in (MI355_GEMV_RESIDENT=1) for wide-N shapes.
-    static const bool use_res = getenv("MI355_GEMV_RESIDENT") != nullptr;
-    if (lds <= 96 * 1024 && use_res) {
-      static bool attr_set = false;  // benign race: the attribute is idempotent
-      if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemv_res_kernel<MT, 2, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        MI355_REQUIRE(e == hipSuccess, "gemv: cannot reserve LDS: %s", hipGetErrorString(e));
-        attr_set = true;
-      }
-      const int ngroups = (a.N + 1) / 2;
-      const int per_cu = lds <= 24 * 1024 ? 4 : (lds <= 48 * 1024 ? 3 : (lds <= 72 * 1024 ? 2 : 1));
-      int blocks = (ngroups + 3) / 4;
-      if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-      MI355_CLEAR_ERROR();
-      hipLaunchKernelGGL((gemv_res_kernel<MT, 2, WT>), dim3(blocks), dim3(256), lds, st, a, ngroups);
-      MI355_LAUNCH_CHECK("gemv(resident)");
-      return MI355_OK;
-    }
-  }
+  // byte, which is what binds at 8 rows (16 LDS bytes per weight byte at NC = 1) and for very wide outputs; SwiGLU / rotary pairs always need 2.
+  // (Staging the rows once per workgroup and walking many column groups was measured slower at M = 8, 22.0 us vs 18.9 us per launch,
+  // profiles/r1_kernel_stats_qwen3_1p7b_b8_v4_resident.txt: these launches are bound by their dependent chain -- statistics -> staging -> first
+  // weight slice -- not by the re-staging of x, and this kernel overlaps the weight latency with the staging.)
+  const int nc = (a.glu || a.rope_cos || MT >= 8 || a.N >= 16384) ? 2 : 1;
   MI355_CLEAR_ERROR();
   if (nc == 2) hipLaunchKernelGGL((gemv_kernel<MT, 2, WT>), dim3((a.N + 7) / 8), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((gemv_kernel<MT, 1, WT>), dim3((a.N + 3) / 4), dim3(256), 0, st, a);
@@ -1098,9 +730,8 @@ int launch_gemv(const mi355_gemv_args& a, hipStream_t st) {
 
 template <int WT>
 int launch_gemv_m(const mi355_gemv_args& a, hipStream_t st) {
-  static const bool m1_old = getenv("MI355_GEMV_M1") != nullptr && getenv("MI355_GEMV_M1")[0] == '0';  // A/B knob: the chunked kernel at one row
   // split K needs a plain epilogue (no SwiGLU pairs / rotary pairs: those shapes have K <= 2048 in every model of the path) and no fused norm
-  if (a.M == 1 && (!m1_old || a.x_ids) && (a.K <= 2048 || (!a.norm && !a.glu && !a.rope_cos))) return launch_gemv1<WT>(a, st);
+  if (a.M == 1 && (a.K <= 2048 || (!a.norm && !a.glu && !a.rope_cos))) return launch_gemv1<WT>(a, st);
   if (a.M == 1) return launch_gemv<1, WT>(a, st);
   if (a.M == 2) return launch_gemv<2, WT>(a, st);
   if (a.M <= 4) return launch_gemv<4, WT>(a, st);
@@ -1150,8 +781,6 @@ extern "C" int mi355_gemv(const mi355_gemv_args* ap, void* stream) {
                 "gemv: the attention prologue needs one row, K = heads * dh <= 2048, <= 32 heads, 1..64 cached positions and a plain input side");
   MI355_REQUIRE(a.w_policy == 0 || a.w_policy == 1, "gemv: w_policy must be 0 (default) or 1 (non-temporal)");
   if (a.out_scale == 0.f) a.out_scale = 1.f;
-  static const bool two_reads = getenv("MI355_GEMV_TWO_READS") != nullptr;  // A/B knob: statistics from a separate read of x (the older schedule)
-  a.norm_two_reads = two_reads ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
   if (a.M > 8) return mi355_gemm_rows_launch(a, st);
   if (mi355_gemv_mfma_eligible(a)) return mi355_gemv_mfma_launch(a, st);

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void gemv_mfma_kernel(const mi355_gemv_args a)
 
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   int it = 0;  // index of this wave's next step: s = wave + 4 * it
-  for (int k0 = 0; k0 < K; k0 += KC) {
+  for (int k0 = 0; k0 < K; k0 += KC) {   // runs once (K <= kKC); kept as a loop: collapsing it changes the generated code of a kernel that is not otherwise touched
     const int kc = K - k0 < KC ? K - k0 : KC;  // multiple of 64
     // ---- stage the chunk: thread t owns the 8-column groups q = t, t + 256, ... of EVERY row (norm weight / bias loaded once per column)
     __syncthreads();  // the previous chunk's readers are done
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void gemv_mfma_kernel(const mi355_gemv_args a)
         __syncthreads();
         if (tid < 8) {
           const float var = ((st_part[0][tid] + st_part[1][tid]) + (st_part[2][tid] + st_part[3][tid])) / (float)K;
-          st_rstd[tid] = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps);
+          st_rstd[tid] = norm_rstd(a.norm, var, a.norm_eps);
         }
         __syncthreads();
 #pragma unroll
@@ -200,235 +200,19 @@ __global__ __launch_bounds__(256) void gemv_mfma_kernel(const mi355_gemv_args a)
   linear_finish(a, m, n, v0);
 }
 
-// ---------------------------------------------------------------------------------------------- streaming variant (no fused norm, any K % 64 == 0)
-// Without a fused norm nothing forces the workgroup to see whole rows, so each WAVE stages only the x columns of ITS OWN k steps, in a private 2 KB
-// LDS window, and there is no workgroup barrier before the final split-K reduction: lane (row = lane >> 3, part = lane & 7) loads the 8 floats
-// x[row][64 s + 8 part .. + 8) of step s (prefetched kDX steps ahead next to the weight ring), splits them into the hi / lo images and writes one
-// 16-byte piece each in the same fragment order as above; the LDS queue of a wave is in order, a wave-level fence separates write and read.
-// Opt-in (MI355_GEMV_MFMA_STREAM, see stream_mode below): measured slower than the FMA kernel on the K > 2048 down projections.
-constexpr int kDX = 4;
-
-template <bool F16>
-__global__ __launch_bounds__(256) void gemv_mfma_stream_kernel(const mi355_gemv_args a) {
-  __shared__ __attribute__((aligned(16))) uint4 win[4][2][64];   // [wave][image][piece]
-  __shared__ float red[4][256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n0 = blockIdx.x * 16;
-  const int K = a.K, M = a.M;
-  const int steps_total = K >> 6;
-  const int gi = lane >> 4, li = lane & 15;
-  const int nrow = n0 + li < a.N ? n0 + li : a.N - 1;
-  const uint16_t* wrow = a.w + (int64_t)nrow * a.ldw + 16 * gi;
-  const int xr = lane >> 3, xp = lane & 7;                       // staging role: input row / 8-column part of the step
-  const float* xrow = a.x + (int64_t)(xr < M ? xr : 0) * a.ldx + 8 * xp;
-  const int wpiece = ((xp & 1) * 4 + (xp >> 1)) * 8 + xr;        // (half, group, row) of the piece this lane writes
-
-  uint4 ring[kD][2];
-  float4 xring[kDX][2];
-  auto issue_w = [&](const int s, uint4 (&dst)[2]) {
-    const uint16_t* p = wrow + ((int64_t)s << 6);
-    dst[0] = *(const uint4*)p;
-    dst[1] = *(const uint4*)(p + 8);
-  };
-  auto issue_x = [&](const int s, float4 (&dst)[2]) {
-    if (xr < M) {
-      const float* p = xrow + ((int64_t)s << 6);
-      dst[0] = *(const float4*)p;
-      dst[1] = *(const float4*)(p + 4);
-    } else {
-      dst[0] = dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-#pragma unroll
-  for (int d = 0; d < kD; ++d)
-    if (wave + 4 * d < steps_total) issue_w(wave + 4 * d, ring[d]);
-#pragma unroll
-  for (int d = 0; d < kDX; ++d)
-    if (wave + 4 * d < steps_total) issue_x(wave + 4 * d, xring[d]);
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int it = 0;; ++it) {
-    const int s = wave + 4 * it;
-    if (s >= steps_total) break;
-    uint4 w0, w1;
-    float4 x0, x1;
-    const int slot = it % kD, xslot = it % kDX;
-#pragma unroll
-    for (int d = 0; d < kD; ++d) {
-      if (slot == d) {
-        w0 = ring[d][0];
-        w1 = ring[d][1];
-        if (s + 4 * kD < steps_total) issue_w(s + 4 * kD, ring[d]);
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < kDX; ++d) {
-      if (xslot == d) {
-        x0 = xring[d][0];
-        x1 = xring[d][1];
-        if (s + 4 * kDX < steps_total) issue_x(s + 4 * kDX, xring[d]);
-      }
-    }
-    uint4 hi, lo;
-    split_hi_lo<F16>(x0.x, x0.y, hi.x, lo.x);
-    split_hi_lo<F16>(x0.z, x0.w, hi.y, lo.y);
-    split_hi_lo<F16>(x1.x, x1.y, hi.z, lo.z);
-    split_hi_lo<F16>(x1.z, x1.w, hi.w, lo.w);
-    wave_lds_fence();   // the previous step's fragment reads are done (in-order LDS queue of the wave)
-    win[wave][0][wpiece] = hi;
-    win[wave][1][wpiece] = lo;
-    wave_lds_fence();
-    const int p0 = (0 * 4 + gi) * 8 + (li & 7), p1 = (1 * 4 + gi) * 8 + (li & 7);
-    const uint4 h0 = win[wave][0][p0], h1 = win[wave][0][p1], l0 = win[wave][1][p0], l1 = win[wave][1][p1];
-    acc = mfma_16x16x32<F16>(w0, h0, acc);
-    acc = mfma_16x16x32<F16>(w1, h1, acc);
-    acc = mfma_16x16x32<F16>(w0, l0, acc);
-    acc = mfma_16x16x32<F16>(w1, l1, acc);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[wave][(4 * gi + r) * 16 + li] = acc[r];
-  __syncthreads();
-  const int i = tid & 15, m = tid >> 4;
-  const int n = n0 + i;
-  if (m >= M || n >= a.N) return;
-  const float v0 = (red[0][i * 16 + m] + red[1][i * 16 + m]) + (red[2][i * 16 + m] + red[3][i * 16 + m]);
-  if (a.glu) {
-    if (i & 1) return;
-    const float v1 = (red[0][(i + 1) * 16 + m] + red[1][(i + 1) * 16 + m]) + (red[2][(i + 1) * 16 + m] + red[3][(i + 1) * 16 + m]);
-    linear_finish_glu(a, m, n, v0, v1);
-    return;
-  }
-  linear_finish(a, m, n, v0);
-}
-
-// ---------------------------------------------------------------------------------------------- K split over workgroups (no fused norm, K > 2048)
-// The down projections (N = 1024 .. 2048, K = 3072 .. 8192) have few column tiles and a long K: N / 16 workgroups walking 2-4 chunks one after the
-// other leave the chip empty (measured: slower than the FMA kernel, call 24).  Here a workgroup owns ONE (tile, 2048-column chunk) pair -- the grid is
-// tiles x chunks -- and the chunks of a tile meet through a scratch record and a ticket: the workgroup that draws the last ticket adds the records
-// in chunk order (deterministic) and runs the epilogue.  Nobody waits for anybody.
-template <bool F16>
-__global__ __launch_bounds__(256) void gemv_mfma_ksplit_kernel(const mi355_gemv_args a, const int nch) {
-  __shared__ __attribute__((aligned(16))) uint4 planes[2 * kKC * 8 / 8];  // [2 images][32 steps][2 halves][4 groups][8 rows] 16-byte pieces: 64 KB
-  __shared__ float red[4][256];
-  __shared__ int ticket_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tile = blockIdx.x, c = blockIdx.y;
-  const int n0 = tile * 16;
-  const int K = a.K, M = a.M;
-  const int k0 = c * kKC;
-  const int kc = K - k0 < kKC ? K - k0 : kKC;   // multiple of 64
-  const int steps = kc >> 6;
-  constexpr int img = kKC;                      // 16-byte pieces per image
-  const int gi = lane >> 4, li = lane & 15;
-  const int nrow = n0 + li < a.N ? n0 + li : a.N - 1;
-  const uint16_t* wrow = a.w + (int64_t)nrow * a.ldw + k0 + 16 * gi;
-  uint4 ring[kD][2];
-#pragma unroll
-  for (int d = 0; d < kD; ++d) {
-    ring[d][0] = ring[d][1] = make_uint4(0u, 0u, 0u, 0u);
-    if (wave + 4 * d < steps) {
-      const uint16_t* p = wrow + ((int64_t)(wave + 4 * d) << 6);
-      ring[d][0] = *(const uint4*)p;
-      ring[d][1] = *(const uint4*)(p + 8);
-    }
-  }
-  {  // stage the chunk: thread t owns the 8-column group q = t of every row
-    const int q = tid, k = q * 8;
-    if (k < kc) {
-      const int step = q >> 3, r = q & 7, g = r >> 1, h = r & 1;
-      const int base = ((step * 2 + h) * 4 + g) * 8;
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        float4 xa = make_float4(0.f, 0.f, 0.f, 0.f), xb = xa;
-        if (m < M) {
-          const float* p = a.x + (int64_t)m * a.ldx + k0 + k;
-          xa = *(const float4*)p;
-          xb = *(const float4*)(p + 4);
-        }
-        uint4 hi, lo;
-        split_hi_lo<F16>(xa.x, xa.y, hi.x, lo.x);
-        split_hi_lo<F16>(xa.z, xa.w, hi.y, lo.y);
-        split_hi_lo<F16>(xb.x, xb.y, hi.z, lo.z);
-        split_hi_lo<F16>(xb.z, xb.w, hi.w, lo.w);
-        planes[base + m] = hi;
-        planes[img + base + m] = lo;
-      }
-    }
-  }
-  __syncthreads();
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int d = 0; d < kD; ++d) {
-    const int sl = wave + 4 * d;
-    if (sl < steps) {
-      const int p0 = ((sl * 2 + 0) * 4 + gi) * 8 + (li & 7);
-      const int p1 = ((sl * 2 + 1) * 4 + gi) * 8 + (li & 7);
-      acc = mfma_16x16x32<F16>(ring[d][0], planes[p0], acc);
-      acc = mfma_16x16x32<F16>(ring[d][1], planes[p1], acc);
-      acc = mfma_16x16x32<F16>(ring[d][0], planes[img + p0], acc);
-      acc = mfma_16x16x32<F16>(ring[d][1], planes[img + p1], acc);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[wave][(4 * gi + r) * 16 + li] = acc[r];
-  __syncthreads();
-  const int i = tid & 15, m = tid >> 4;   // consecutive threads -> consecutive output columns n of one input row m
-  const int n = n0 + i;
-  float v0 = (red[0][i * 16 + m] + red[1][i * 16 + m]) + (red[2][i * 16 + m] + red[3][i * 16 + m]);
-  if (nch > 1) {
-    float* rec = a.split_ws + ((int64_t)tile * nch + c) * 256;
-    rec[tid] = v0;
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) ticket_s = atomicAdd(a.split_cnt + tile, 1);
-    __syncthreads();
-    if (ticket_s != nch - 1) return;
-    __threadfence();
-    const float* recs = a.split_ws + (int64_t)tile * nch * 256;
-    v0 = 0.f;
-    for (int cc = 0; cc < nch; ++cc) v0 += __hip_atomic_load(recs + cc * 256 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) a.split_cnt[tile] = 0;   // leave the ticket zeroed for the next launch
-  }
-  if (m >= M || n >= a.N) return;
-  linear_finish(a, m, n, v0);
-}
-
 }  // namespace
 
 // 1 = this call qualifies for the matrix-pipe kernel (mi355_gemv dispatches here unless MI355_GEMV_MFMA=0)
-// MI355_GEMV_MFMA_STREAM: 0 (default) = streaming variant off: K > 2048 stays on the FMA kernel; 1 = for images the staged kernel cannot take
-// (no fused norm, K > 2048); 2 = for every call without a fused norm.  Parity-green in both modes (GPU call 35), but with N / 16 workgroups a wave
-// streams its whole K slice serially: Qwen3-TTS-1.7B ran 8.55 ms per frame with mode 1 against 7.81 with the FMA kernel on those images (24
-// steps per wave at K = 6144), so it is an A/B harness until it splits K over more waves.
-static int stream_mode() {
-  static const int mode = getenv("MI355_GEMV_MFMA_STREAM") ? atoi(getenv("MI355_GEMV_MFMA_STREAM")) : 0;
-  return mode;
-}
-
-static bool ksplit_on() {
-  static const bool on = getenv("MI355_GEMV_KSPLIT") != nullptr && getenv("MI355_GEMV_KSPLIT")[0] == '1';
-  return on;
-}
-
-static bool use_stream(const mi355_gemv_args& a) {
-  if (a.norm) return false;
-  return stream_mode() == 2 || (stream_mode() == 1 && a.K > kKC);
-}
-
 int mi355_gemv_mfma_eligible(const mi355_gemv_args& a) {
   static const bool off = getenv("MI355_GEMV_MFMA") != nullptr && getenv("MI355_GEMV_MFMA")[0] == '0';
   if (off) return 0;
   if (a.M < 5 || a.M > 8 || a.rope_cos) return 0;
   if (a.wdtype != MI355_W_BF16 && a.wdtype != MI355_W_F16) return 0;
   if (a.K % 64 || a.K < 64 || a.ldw % 8 || ((uintptr_t)a.w) % 16 || a.ldx % 4 || ((uintptr_t)a.x) % 16) return 0;
-  // the staged kernel holds one chunk: its chunk loop's workgroup barriers were measured to cost more than they save (r1 call 26);
-  // MI355_GEMV_MFMA_CHUNKED=1 lets no-norm images with K > 2048 take the chunk loop anyway (A/B knob)
-  static const bool chunked = getenv("MI355_GEMV_MFMA_CHUNKED") != nullptr && getenv("MI355_GEMV_MFMA_CHUNKED")[0] == '1';
-  // K split over workgroups (gemv_mfma_ksplit_kernel): OPT-IN (MI355_GEMV_KSPLIT=1).  Measured in call 29: 19.7 / 43.5 us per launch on the Qwen3
-  // down projections against 13.9 / 20.1 us for the FMA kernel -- the agent-scope fence in front of the ticket writes the L2 back, which costs
-  // more than the extra workgroups bring (the same finding as the key-split attention of round 1)
-  if (ksplit_on() && a.K > kKC && !a.norm && !a.glu && a.split_ws && a.split_cnt) return 1;
-  if (a.K > kKC && !use_stream(a) && !(chunked && !a.norm)) return 0;
+  // The staged kernel holds one chunk; K > 2048 (the down projections) stays on the FMA kernel.  Every matrix-pipe form tried there measured
+  // slower: more chunks behind workgroup barriers, a per-wave streamed x window, and K split over workgroups with a ticket (profiles/README.md,
+  // docs/DECODE_RUNNERS.md).
+  if (a.K > kKC) return 0;
   if (a.glu && (a.N % 2)) return 0;
   return 1;
 }
@@ -437,22 +221,7 @@ int mi355_gemv_mfma_launch(const mi355_gemv_args& a, hipStream_t st) {
   static bool attr_set[2] = {false, false};  // benign race: the attribute is idempotent
   const bool f16 = a.wdtype == MI355_W_F16;
   const dim3 grid((a.N + 15) / 16);
-  if (ksplit_on() && a.K > kKC && !a.norm && !a.glu && a.split_ws && a.split_cnt && !use_stream(a)) {
-    const int nch = (a.K + kKC - 1) / kKC;
-    MI355_CLEAR_ERROR();
-    if (f16) hipLaunchKernelGGL(gemv_mfma_ksplit_kernel<true>, dim3(grid.x, nch), dim3(256), 0, st, a, nch);
-    else hipLaunchKernelGGL(gemv_mfma_ksplit_kernel<false>, dim3(grid.x, nch), dim3(256), 0, st, a, nch);
-    MI355_LAUNCH_CHECK("gemv(mfma, K split over workgroups)");
-    return MI355_OK;
-  }
-  if (use_stream(a)) {
-    MI355_CLEAR_ERROR();
-    if (f16) hipLaunchKernelGGL(gemv_mfma_stream_kernel<true>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(gemv_mfma_stream_kernel<false>, grid, dim3(256), 0, st, a);
-    MI355_LAUNCH_CHECK("gemv(mfma stream)");
-    return MI355_OK;
-  }
-  const size_t lds = (size_t)(a.K < kKC ? a.K : kKC) * 32;
+  const size_t lds = (size_t)a.K * 32;   // K <= kKC (mi355_gemv_mfma_eligible)
   if (!attr_set[f16]) {
     hipError_t e = f16 ? hipFuncSetAttribute((const void*)gemv_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kKC * 32)
                        : hipFuncSetAttribute((const void*)gemv_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kKC * 32);

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_arg
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
           const float var = s[m] / (float)K;
-          const float rs = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps);
+          const float rs = norm_rstd(a.norm, var, a.norm_eps);
           const float mu = mean[m];
           xa[m] = make_float4((xa[m].x - mu) * rs * wa.x + ba.x, (xa[m].y - mu) * rs * wa.y + ba.y, (xa[m].z - mu) * rs * wa.z + ba.z,
                               (xa[m].w - mu) * rs * wa.w + ba.w);

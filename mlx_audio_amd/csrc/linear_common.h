@@ -8,6 +8,7 @@
 // kFp8Unbias): which product joins which fma is decided by the expression around the call after inlining, and the helpers add no floating-point
 // operation of their own and reorder none.  A new activation or destination type is added here, once; a new epilogue operand in the two forms of
 // the tail below and in rows_finish_kernel (why they are not one function is said where they are defined).
+// Also here, once: the fused input norm's 1 / std tail and k-loop row statistics, and the convert-and-FMA step of one k-slice (gemv.hip).
 #pragma once
 #include "common.h"
 
@@ -46,6 +47,41 @@ __device__ __forceinline__ f32x4 mfma_16x16x32(const uint4 a, const uint4 b, con
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
+// ---------------------------------------------------------------------------------------------- the fused input norm's row statistics
+// 1 / std of a row from its variance (or, for RMSNorm, its mean square).  norm = mi355_gemv_args.norm: 1 LayerNorm (divide and square root), 2 RMSNorm
+__device__ __forceinline__ float norm_rstd(const int norm, const float var, const float eps) { return norm == 1 ? 1.0f / sqrtf(var + eps) : rsqrtf(var + eps); }
+
+// Two-pass statistics of one row of K floats (K % 4 == 0; global memory or LDS), computed by a whole wave: lane l reads the float4 pieces at
+// k = 4 l, 4 l + 256, ...  The sum and then the centred second moment (RMSNorm: mean = 0) each add a piece as (x + y) + (z + w) and finish
+// with wave_sum.  Lane 0 stores the mean and rstd of this row, m, into the workgroup's LDS tables (rstd is formed under that branch, by one lane).
+__device__ __forceinline__ void norm_row_stats(const float* xr, const int K, const int lane, const int norm, const float eps, float* st_mean, float* st_rstd,
+                                               const int m) {
+  float s = 0.f, q = 0.f;
+  for (int k = lane * 4; k < K; k += 256) { const float4 t = *(const float4*)(xr + k); s += (t.x + t.y) + (t.z + t.w); }
+  const float mean = norm == 1 ? wave_sum(s) / (float)K : 0.f;
+  for (int k = lane * 4; k < K; k += 256) {
+    const float4 t = *(const float4*)(xr + k);
+    const float d0 = t.x - mean, d1 = t.y - mean, d2 = t.z - mean, d3 = t.w - mean;
+    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  }
+  const float var = wave_sum(q) / (float)K;
+  if (lane == 0) { st_mean[m] = mean; st_rstd[m] = norm_rstd(norm, var, eps); }
+}
+
+// ---------------------------------------------------------------------------------------------- one k-slice of the FMA kernels (gemv.hip)
+// NC columns' 16-byte weight pieces against this lane's EPL input values of row m: each piece is converted (cvt_w16) and joins its column's
+// running sum through EPL fmaf, in element order
+template <int WT, int NC, int MT>
+__device__ __forceinline__ void gemv_slice_fma(const uint4 (&w)[NC], const float (&xv)[mi355_wt<WT>::EPL], float (&acc)[NC][MT], const int m) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    float wf[mi355_wt<WT>::EPL];
+    cvt_w16<WT>(w[c], wf);
+#pragma unroll
+    for (int j = 0; j < mi355_wt<WT>::EPL; ++j) acc[c][m] = fmaf(xv[j], wf[j], acc[c][m]);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- the tail's store, and the SwiGLU value
 // out_scale, then y or -- for columns past `split` -- the y2 slot in its element type (e.g. q -> y, k | v -> the KV-cache slot)
 __device__ __forceinline__ void linear_store(const mi355_gemv_args& a, const int m, const int n, const float v) {
@@ -70,7 +106,7 @@ __device__ __forceinline__ void linear_finish_regs(const mi355_gemv_args& a, con
 // ---------------------------------------------------------------------------------------------- the whole tail, operand loads included
 // What a thread that owns output (m, n) calls once s is complete: absent operands are not loaded.  GLU: n = the gate's (even) column.
 // Same arithmetic as linear_finish_regs, written out rather than built on it: with colscale as a value the multiply by an absent colscale's 1.0
-// is no longer skipped, and every caller (the matrix-pipe kernels, gemv1_splitk_old_kernel) compiles to one v_mul_f32 fewer and a different
+// is no longer skipped, and every caller (the matrix-pipe kernels) compiles to one v_mul_f32 fewer and a different
 // schedule.  rows_finish_kernel (its own argument struct, eight columns per thread) keeps its tail for the same reason: its adds re-fuse.
 __device__ __forceinline__ void linear_finish(const mi355_gemv_args& a, const int m, const int n, const float s) {
   float v = linear_act(s + (a.bias ? a.bias[n] : 0.f), a.post_act, a.post_slope) * (a.colscale ? a.colscale[n] : 1.f);

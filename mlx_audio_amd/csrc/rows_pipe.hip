@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(const mi355_rows_finis
     if (lane == 0) sred[4 + wave] = q;
     __syncthreads();
     const float var = ((sred[4] + sred[5]) + (sred[6] + sred[7])) / (float)No;
-    rstd = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps);
+    rstd = norm_rstd(a.norm, var, a.norm_eps);
   }
 #pragma unroll
   for (int it = 0; it < kMaxPieces; ++it) {
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256) void rows_finish_lean_kernel(const mi355_rows_
     if (lane == 0) sred[4 + wave] = q;
     __syncthreads();
     const float var = ((sred[4] + sred[5]) + (sred[6] + sred[7])) / (float)No;
-    rstd = a.norm == 1 ? 1.0f / sqrtf(var + a.norm_eps) : rsqrtf(var + a.norm_eps);
+    rstd = norm_rstd(a.norm, var, a.norm_eps);
   }
   uint4* const pl = (uint4*)a.planes;
   // every load has long landed; an opaque use makes the compiler say so HERE -- behind the conditional y stores its wait-count bookkeeping can no

@@ -369,7 +369,10 @@ def _gemv_tol(M, K, f16, base=5e-6):
 
 
 @pytest.mark.parametrize("mode,M,K", [("layer", 1, 768), ("layer", 5, 3072), ("rms", 8, 2048), ("rms", 2, 1024), ("rms", 1, 2048), ("rms", 1, 1024),
-                                      ("layer", 1, 2048), ("layer", 1, 3072)])
+                                      ("layer", 1, 2048), ("layer", 1, 3072),
+                                      # the statistics branches of gemv_kernel: 2..4 rows from the staged LDS copy / a k-loop over two chunks,
+                                      # 8-row tiles off the matrix pipe (K % 64 != 0) from LDS / two rows per wave in registers, one row past 4096
+                                      ("rms", 3, 1024), ("layer", 3, 2304), ("layer", 6, 200), ("rms", 7, 1096), ("layer", 2, 4352), ("rms", 1, 4104)])
 def test_gemv_fused_norm_and_split(ops, mode, M, K):
     g = torch.Generator().manual_seed(K + M)
     Nq, Nkv = 256, 128

@@ -2,7 +2,7 @@
 """Launch-period microbenchmark of mi355_gemv on the decode-step shapes of the three autoregressive configs (Whisper-small decoder, Qwen3-TTS-1.7B
 talker / code predictor, CSM-1B backbone / depth decoder): N back-to-back launches of one shape on one stream (each waits for its predecessor, like the
 dependent chain of a decode step), events around the batch.  Prints one line per shape: us per launch, weight GB/s, fraction of the 8 TB/s HBM peak.
-A/B knobs are environment variables read by the library (MI355_GEMV_TWO_READS=1: the older fused-norm schedule)."""
+A/B knobs are environment variables read by the library (MI355_GEMV_MFMA=0: the FMA kernel at 5..8 rows; MI355_LIB_PATH: another build of it)."""
 import argparse
 import json
 import os

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel generated-code comparison of two source trees: the evidence a refactor that must not change the kernels commits.
-usage: tools/codegen_diff.py OLD_CSRC NEW_CSRC file.hip [file.hip ...]   (e.g. OLD_CSRC = `git worktree add` of the parent, NEW_CSRC = mlx_audio_amd/csrc)
+usage: tools/codegen_diff.py OLD_CSRC NEW_CSRC file.hip [file.hip ...] [--allow-removed]   (e.g. OLD_CSRC = `git worktree add` of the parent, NEW_CSRC = mlx_audio_amd/csrc)
+--allow-removed: kernels that exist only in OLD_CSRC are listed, not counted as a failure (a change that deletes kernels); new ones still fail.
 
 Every file is compiled for gfx950 to assembly with exactly build.py's flags (COMMON_FLAGS and the file's EXTRA_FLAGS).  Per kernel it compares
   * the resources of hipcc's kernel-resource-usage remarks (VGPRs, AGPRs, SGPRs, scratch, spills, LDS, occupancy): must be equal;
@@ -43,7 +44,9 @@ def compile_one(csrc, name, out):
 
 
 def main():
-    old, new, files = sys.argv[1], sys.argv[2], sys.argv[3:]
+    argv = [x for x in sys.argv[1:] if x != "--allow-removed"]
+    allow_removed = len(argv) != len(sys.argv) - 1
+    old, new, files = argv[0], argv[1], argv[2:]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         for name in files:
@@ -51,8 +54,10 @@ def main():
             r1, h1, t1 = compile_one(new, name, os.path.join(tmp, "new.s"))
             print("== %s: %d kernels" % (name, len(r1)))
             if set(r0) != set(r1):
-                bad += 1
-                print("   FAIL kernel symbols differ: only old %s, only new %s" % (sorted(set(r0) - set(r1)), sorted(set(r1) - set(r0))))
+                removed_only = allow_removed and not set(r1) - set(r0)
+                bad += not removed_only
+                print("   %s kernel symbols differ: only old %s, only new %s" % ("removed" if removed_only else "FAIL",
+                      sorted(demangle(k) for k in set(r0) - set(r1)), sorted(demangle(k) for k in set(r1) - set(r0))))
             for k in sorted(set(r0) & set(r1)):
                 dem = demangle(k)
                 resd = [(q, r0[k].get(q), r1[k].get(q)) for q in RES if r0[k].get(q) != r1[k].get(q)]
