@@ -1515,6 +1515,111 @@ typedef struct {
 } mi355_gated_fsmn_args;
 int mi355_gated_fsmn(const mi355_gated_fsmn_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FireRedASR2-AED (stt/models/fireredasr2/fireredasr2.py): the Conv2dSubsampling convs, the middle of the Conformer convolution module with its
+ * LayerNorm over 2 x d_model channels, one step of the decoder's beam search and the decoder self-attention over a cache that is never
+ * re-gathered (firered.hip).  Four entry points added to ABI 37 (new structs and functions only; no existing layout changed).  Plain float32,
+ * no atomics, nothing allocated; every sum runs in a fixed order that depends on neither the launch geometry, nor the batch size, nor the other
+ * items' lengths: two calls on the same bytes give the same bits, and an item inside a ragged batch is bit-equal to that item alone.  A call
+ * that is refused (MI355_ERR_ARG / MI355_ERR_UNSUPPORTED) launches nothing and leaves every output untouched.
+ * ------------------------------------------------------------------------------------------ */
+#define MI355_SUBSAMPLE2D_MAX_COUT 64
+/* The dense 3 x 3 / stride 2 convs of Conv2dSubsampling (fireredasr2.py:17-39): no padding, To = (T - 3) / 2 + 1, Fo = (F - 3) / 2 + 1,
+ *   y[b, t, f, co] = act( bias[co] + sum_{kh, kw, ci} w[co, kh, kw, ci] * x[b, 2 t + kh, 2 f + kw, ci] ),
+ * an fmaf chain from the bias in (kh, kw, ci) order.  x is [B, T, F] for Cin == 1 and channels-last [B, T, F, Cin] otherwise; w is
+ * [Cout, 3, 3, Cin] (the reference's NHWC weight).  Input rows at or beyond lens_in[b] read as zero (the encoder's six zero frames of right
+ * context arise this way for every item of a padded batch); output rows at or beyond lens_out[b] are written as zeros.  out_cf == 0 writes
+ * y [B, To, Fo, Cout]; out_cf == 1 writes y [B, To, Cout, Fo], whose rows of Cout * Fo are in the reference's c * Fo + f order (what
+ * Conv2dSubsampling.out reads after its transpose).  Cin is 1 or Cout; Cout a multiple of 4, <= MI355_SUBSAMPLE2D_MAX_COUT; T, F >= 3, else
+ * MI355_ERR_ARG.  The weights are staged in LDS, Cout * 9 * Cin floats. */
+typedef struct {
+  const float* x; int64_t x_bstride;                     /* [B, T, F (, Cin)] */
+  const float* w; const float* bias;                     /* [Cout, 3, 3, Cin]; [Cout] nullable => 0 */
+  int32_t B; int32_t T; int32_t F; int32_t Cin; int32_t Cout; int32_t relu; int32_t out_cf;
+  const int32_t* lens_in; const int32_t* lens_out;       /* [B] nullable => T / To */
+  float* y; int64_t y_bstride;                           /* [B, To, Fo, Cout] or [B, To, Cout, Fo] */
+} mi355_subsample2d_k3s2_args;
+int mi355_subsample2d_k3s2(const mi355_subsample2d_k3s2_args* a, void* stream);
+
+#define MI355_GLU_DWCONV_LN_MAX_TAPS 33
+#define MI355_GLU_DWCONV_LN_MAX_C 2560
+#define MI355_GLU_DWCONV_LN_ROWS 32     /* rows of one workgroup's tile (the register-window run of dw_window.h); half of it in launches of fewer than 256 such tiles */
+/* ConformerConvolution.__call__ between its two pointwise convs (fireredasr2.py:111-116), channels-last.  x [B, L, 2 C] is pointwise conv 1's
+ * output; with g[t, c] = x[t, c] * sigmoid(x[t, C + c]) for 0 <= t < lens[b] and 0 elsewhere:
+ *   z[t, c] = sum_{k<K} w[c, k] * g[t + k - (K - 1) / 2, c]                       (no bias; an fmaf chain from zero, k ascending)
+ *   n[t, c] = (z[t, c] - mean_t) / sqrt(var_t + eps) * ln_w[c] + ln_b[c]           (mean, then the mean of the squared deviations, over the C channels)
+ *   y[t, c] = n * sigmoid(n)                                                       (full-precision expf)
+ * rows lens[b] <= t < L are written as zeros.  One workgroup owns MI355_GLU_DWCONV_LN_ROWS rows across ALL C channels: z stays in registers
+ * (thread i of NT holds the channels i, i + NT, ...; NT = 256 for C <= 1024 and 512 above, a function of C alone), so per row the traffic is
+ * 2 C floats in (twice for K > 1: the halo of the neighbouring tile, from L2) and C floats out.  Each row statistic is summed per thread over
+ * its channels in ascending order, per wave by the DPP sum, and over the waves as (w0 + w1) + (w2 + w3) (NT = 256) or serially from wave 0
+ * (NT = 512).  The register window holds 1, 15 or 33 taps and a shorter kernel is centred in the next larger one with zero taps around it:
+ * for K other than 1, 15 and 33 the rows up to 7 (K < 15) or 16 (K < 33) steps outside the kernel's own reach are read and gated too, and a
+ * non-finite x there gives NaN (0 * inf) where the sum over K taps alone would not; finite x is the caller's contract.  K odd,
+ * <= MI355_GLU_DWCONV_LN_MAX_TAPS; C a multiple of 4, <= MI355_GLU_DWCONV_LN_MAX_C; y must not alias x; else MI355_ERR_ARG. */
+typedef struct {
+  const float* x; int64_t x_bstride; int32_t ldx;        /* [B, L, ldx], ldx >= 2 C */
+  const float* w;                                        /* [C, K] */
+  const float* ln_w; const float* ln_b; float eps;       /* [C]; [C] */
+  int32_t K; int32_t C; int32_t L; const int32_t* lens; int32_t B;   /* lens [B] nullable => L */
+  float* y; int64_t y_bstride; int32_t ldy;              /* [B, L, ldy] */
+} mi355_glu_dwconv_ln_swish_args;
+int mi355_glu_dwconv_ln_swish(const mi355_glu_dwconv_ln_swish_args* a, void* stream);
+
+#define MI355_BEAM_MAX 8
+#define MI355_BEAM_MAX_V 65536
+/* One step of TransformerDecoder.beam_search (fireredasr2.py:404-446) for N utterances of B beams, one workgroup per utterance.
+ * `step[n]` is the length of the utterance's token history so far (the reference's ys.shape[1]: 1 after <sos>), so the histories hold <sos>
+ * at index 0 and the host starts with step = 1, ind[n, j, 0] = j.  For every utterance whose done[n] == 0, in this order:
+ *   u = logits[n * B + i, :] / smoothing;  t_c = log(exp(u_c - max u) / sum_c exp(u_c - max u) + 1e-10);  t_eos *= eos_penalty
+ *   per beam i its B best (t, token), best first; a beam with finished[n, i] != 0 offers (0, eos), (-1e10, eos), ... instead
+ *   the B best of the B x B sums scores[n, i] + t, best first: new beam j continues beam beam_idx[n, j] with token tok and value t
+ *   scores[n, j] = the sum;  finished[n, j] = (tok == eos);  tokens_out[n, j, :step] = tokens_in[n, beam_idx, :step], tokens_out[n, j, step] = tok
+ *   conf_out likewise with exp(t) at index step (nullable pair);  ind_out[n, j, :step] = ind_in[n, beam_idx, :step], ind_out[n, j, step] = j
+ *   done[n] = 1 when all B beams are finished or step + 1 == max_steps[n];  step[n] += 1
+ * An utterance with done[n] != 0 is left UNTOUCHED (no output of it is written, step[n] stays): the host may poll `done` every few steps, and the
+ * final histories of utterance n are in the buffer that its last live step wrote.  An utterance whose step is outside [1, Tmax) only gets
+ * done[n] = 1.  Selection: t is monotone in the logit, so the per-beam candidates are the B largest logits of the row with the eos column taken
+ * out (V / 256 columns per thread, ascending; block_argmax), t is evaluated for those and for eos only, and eos is inserted by its (penalised) t.
+ * TIES (the reference's argpartition leaves them unspecified): everywhere the larger value wins; among equal values the lower beam wins first, then
+ * the lower token id (per beam: equal logits, or an equal t against eos, go to the lower token id; a finished beam's equal entries keep their order).
+ * The max is exact; the sum of exponentials is per thread over its columns ascending, then the wave butterfly and (w0 + w1) + (w2 + w3).
+ * 1 <= B <= MI355_BEAM_MAX, B < V <= MI355_BEAM_MAX_V, 0 <= eos_id < V, smoothing > 0, Tmax >= 2, the *_in and *_out buffers distinct, else
+ * MI355_ERR_ARG. */
+typedef struct {
+  const float* logits; int64_t ld;                       /* [N * B, ld >= V] */
+  int32_t N; int32_t B; int32_t V; int32_t Tmax;
+  int32_t eos_id; float softmax_smoothing; float eos_penalty;
+  float* scores; int32_t* finished;                      /* [N, B] each, in place */
+  int32_t* step; const int32_t* max_steps; int32_t* done; /* [N] each; step and done in place */
+  const int32_t* tokens_in; int32_t* tokens_out;         /* [N, B, Tmax] */
+  const int32_t* ind_in; int32_t* ind_out;               /* [N, B, Tmax] */
+  const float* conf_in; float* conf_out;                 /* [N, B, Tmax] nullable (together) */
+  int32_t* beam_idx; int32_t* new_tokens; float* new_conf; /* [N, B] each; new_conf nullable */
+} mi355_beam_step_args;
+int mi355_beam_step(const mi355_beam_step_args* a, void* stream);
+
+#define MI355_BEAM_ATTN_MAX_TK 4096
+/* DecoderMultiHeadAttention.__call__ behind its projections (fireredasr2.py:272-279) for ONE query per (utterance, beam) over a k / v cache
+ * that is never moved: the k / v rows of position s stay in the slot of the beam that produced them, and beam j of utterance n attends, for
+ * 0 <= s <= pos[n], to row s of slot ind[n, j, s] (the table mi355_beam_step maintains; entries are clamped to [0, B)):
+ *   p_s = softmax_s(scale * q . k[n, ind[n, j, s], s]),   out = sum_s p_s * v[n, ind[n, j, s], s]        (scale, softmax, then @ v)
+ * per head h at columns [h dh, (h + 1) dh).  q / out are [N * B, ld] rows; the caches are [N * B slots, Tk rows, ld].  pos[n] is clamped to
+ * Tk - 1; pos[n] < 0 (an utterance that is done) writes zero rows.  One wave per (utterance, beam, head): the scores of the keys s, s + 64, ...
+ * per lane (an fmaf chain over dh), the exact max, the sum of exponentials per lane ascending and the wave butterfly, then an fmaf chain over
+ * s ascending per output channel.  dh 64 or 128, any number of heads, 1 <= B <= MI355_BEAM_MAX, 1 <= Tk <= MI355_BEAM_ATTN_MAX_TK, Tk <= ld_ind,
+ * rows 16-byte aligned (strides multiples of 4), else MI355_ERR_ARG. */
+typedef struct {
+  const float* q; int32_t ldq;                           /* [N * B, ldq] */
+  const float* k; int64_t k_sstride; int32_t ldk;        /* slot n * B + i at k + (n * B + i) * k_sstride, rows [Tk, ldk] */
+  const float* v; int64_t v_sstride; int32_t ldv;
+  const int32_t* ind; int32_t ld_ind;                    /* [N, B, ld_ind] */
+  const int32_t* pos;                                    /* [N] */
+  int32_t N; int32_t B; int32_t Tk; int32_t heads; int32_t dh; float scale;
+  float* out; int32_t ldo;                               /* [N * B, ldo] */
+} mi355_beam_attention_args;
+int mi355_beam_attention(const mi355_beam_attention_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,29 @@ __device__ __forceinline__ T block_join_sum(T wave_value, T* red) {
   return r;
 }
 
+// R sums at once (the per-row statistics of a tile: one barrier pair for all of them instead of one per row): red holds NW * R floats, the
+// association per sum is block_join_sum's.
+template <int NW, int R>
+__device__ __forceinline__ void block_join_sum_rows(const float (&wave_values)[R], float* red, float (&out)[R]) {
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) red[(threadIdx.x >> 6) * R + i] = wave_values[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    if constexpr (NW == 4) {
+      out[i] = (red[i] + red[R + i]) + (red[2 * R + i] + red[3 * R + i]);
+    } else {
+      float r = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) r += red[w * R + i];
+      out[i] = r;
+    }
+  }
+}
+
 template <int NW>
 __device__ __forceinline__ float block_join_max(float wave_value, float* red) {
   __syncthreads();

@@ -46,9 +46,10 @@ __device__ __forceinline__ float dw_window_row(const int i, const int t0, const 
   return (r >= 0 && r < len) ? row(r) : 0.f;
 }
 
-// output i of the run: start + the taps in order j = 0 .. KMAX - 1
-template <int KMAX>
-__device__ __forceinline__ float dw_tap_sum(const float (&w)[KMAX], const float (&win)[kRun + KMAX - 1], const int i, float acc) {
+// output i of the run: start + the taps in order j = 0 .. KMAX - 1.  RUN: the run's length where a kernel runs shorter ones (firered.hip); an output does
+// not depend on it
+template <int KMAX, int RUN = kRun>
+__device__ __forceinline__ float dw_tap_sum(const float (&w)[KMAX], const float (&win)[RUN + KMAX - 1], const int i, float acc) {
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) acc = fmaf(w[j], win[i + j], acc);
   return acc;

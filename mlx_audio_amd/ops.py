@@ -1945,3 +1945,138 @@ def istft_frames(spec: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor,
                      hop=hop, window=_ptr(window), norm=_ptr(norm), norm_mode=norm_mode, clamp=int(clamp), trim=trim,
                      out_len=out_len, frames_ws=_ptr(ws), out=_ptr(out), ld_out=out.stride(0))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- FireRedASR2-AED (csrc/firered.hip)
+SUBSAMPLE2D_MAX_COUT = 64        # MI355_SUBSAMPLE2D_MAX_COUT
+GLU_DWCONV_LN_MAX_TAPS = 33      # MI355_GLU_DWCONV_LN_MAX_TAPS
+GLU_DWCONV_LN_MAX_C = 2560       # MI355_GLU_DWCONV_LN_MAX_C
+GLU_DWCONV_LN_ROWS = 32          # MI355_GLU_DWCONV_LN_ROWS
+BEAM_MAX = 8                     # MI355_BEAM_MAX
+BEAM_MAX_V = 65536               # MI355_BEAM_MAX_V
+BEAM_ATTN_MAX_TK = 4096          # MI355_BEAM_ATTN_MAX_TK
+
+
+def subsample2d_out(n: int) -> int:
+    """k = 3, stride 2, no padding."""
+    return (n - 3) // 2 + 1
+
+
+def subsample2d_k3s2(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], y: torch.Tensor, *, relu: bool = True, out_cf: bool = False,
+                     lens_in: Optional[torch.Tensor] = None, lens_out: Optional[torch.Tensor] = None):
+    """Dense 3 x 3 / stride 2 conv without padding over (time, frequency) (``mi355_subsample2d_k3s2``): ``x`` [B, T, F] (one input channel) or
+    channels-last [B, T, F, Cin], ``w`` [Cout, 3, 3, Cin], ``y`` [B, To, Fo, Cout], or [B, To, Cout, Fo] with ``out_cf`` (rows in the ``c * Fo + f`` order
+    the subsampler's ``out`` linear reads).  Input rows at and beyond ``lens_in[b]`` read as zero, output rows at and beyond ``lens_out[b]`` are zero."""
+    assert x.dtype == torch.float32 and x.is_cuda and y.dtype == torch.float32 and y.is_cuda and y.dim() == 4 and x.dim() in (3, 4)
+    B, T, F = x.shape[:3]
+    Cin = 1 if x.dim() == 3 else x.shape[3]
+    Cout = w.shape[0]
+    To, Fo = subsample2d_out(T), subsample2d_out(F)
+    assert x[0].is_contiguous() and y[0].is_contiguous()
+    assert tuple(y.shape) == ((B, To, Cout, Fo) if out_cf else (B, To, Fo, Cout)), (tuple(y.shape), tuple(x.shape))
+    assert tuple(w.shape) == (Cout, 3, 3, Cin) and w.is_contiguous() and w.dtype == torch.float32 and w.is_cuda
+    assert bias is None or (bias.numel() == Cout and bias.is_contiguous() and bias.dtype == torch.float32 and bias.is_cuda)
+    _lib.call_struct("mi355_subsample2d_k3s2", "mi355_subsample2d_k3s2_args", _stream(), x=_ptr(x), x_bstride=x.stride(0) if B > 1 else x[0].numel(),
+                     w=_ptr(w), bias=_ptr(bias), B=B, T=T, F=F, Cin=Cin, Cout=Cout, relu=int(relu), out_cf=int(out_cf), lens_in=_lens_arg(lens_in, B),
+                     lens_out=_lens_arg(lens_out, B), y=_ptr(y), y_bstride=y.stride(0) if B > 1 else y[0].numel())
+    return y
+
+
+def glu_dwconv_ln_swish(x: torch.Tensor, w: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, y: torch.Tensor, *, eps: float = 1e-5,
+                        lens: Optional[torch.Tensor] = None):
+    """``swish(LayerNorm_C(sum_k w[:, k] * g[t + k - (K - 1) / 2]))`` with ``g = x[..., :C] * sigmoid(x[..., C:])`` (``mi355_glu_dwconv_ln_swish``): the
+    middle of FireRedASR2's convolution module in one launch, ``x`` [B, L, 2 C] -> ``y`` [B, L, C]; ``w`` [C, K] (K odd, <= ``GLU_DWCONV_LN_MAX_TAPS``),
+    ``ln_w`` / ``ln_b`` [C], C a multiple of 4 up to ``GLU_DWCONV_LN_MAX_C``.  ``g`` is zero outside ``[0, lens[b])``; rows at and beyond ``lens[b]`` are zero."""
+    B, L, C2, xbs, ldx = _nlc(x)
+    By, Ly, C, ybs, ldy = _nlc(y)
+    assert (By, Ly) == (B, L) and C2 == 2 * C
+    f32 = lambda t, n: t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == n
+    assert w.dim() == 2 and w.shape[0] == C and f32(w, w.numel()) and f32(ln_w, C) and f32(ln_b, C)
+    _lib.call_struct("mi355_glu_dwconv_ln_swish", "mi355_glu_dwconv_ln_swish_args", _stream(), x=_ptr(x), x_bstride=xbs, ldx=ldx, w=_ptr(w), ln_w=_ptr(ln_w),
+                     ln_b=_ptr(ln_b), eps=eps, K=w.shape[1], C=C, L=L, lens=_lens_arg(lens, B), B=B, y=_ptr(y), y_bstride=ybs, ldy=ldy)
+    return y
+
+
+@dataclass
+class BeamState:
+    """The device state of ``beam_step`` for N utterances of B beams.  ``tokens`` / ``ind`` / ``conf`` are pairs of [N, B, Tmax] buffers: a step reads
+    ``[cur]`` and writes ``[1 - cur]``, then ``cur`` flips.  An utterance that is done is left untouched by later steps, so its final histories are in
+    the buffer its last live step wrote: index ``step[n] % 2 == 0`` -> buffer 1, else buffer 0 when ``cur`` started at 0 (``final()`` does this)."""
+    scores: torch.Tensor
+    finished: torch.Tensor
+    step: torch.Tensor
+    max_steps: torch.Tensor
+    done: torch.Tensor
+    tokens: Tuple[torch.Tensor, torch.Tensor]
+    ind: Tuple[torch.Tensor, torch.Tensor]
+    conf: Tuple[torch.Tensor, torch.Tensor]
+    beam_idx: torch.Tensor
+    new_tokens: torch.Tensor
+    new_conf: torch.Tensor
+    cur: int = 0
+
+    def final(self):
+        """``(tokens, conf, ind)`` [N, B, Tmax] as each utterance's last live step left them (histories start with <sos> at index 0)."""
+        sel = (self.step % 2 == 0).view(-1, 1, 1)     # step s was written by the call that started at step s - 1 = the (s - 1)-th call
+        pick = lambda pair: torch.where(sel, pair[1], pair[0])
+        return pick(self.tokens), pick(self.conf), pick(self.ind)
+
+
+def beam_state(N: int, B: int, Tmax: int, max_steps, *, sos_id: int, device) -> BeamState:
+    """The state before the first step: scores ``[0, -1e10, ...]``, nothing finished, ``step = 1`` with <sos> at index 0 of every history and
+    ``ind[n, j, 0] = j``.  ``max_steps`` [N] (ints or a tensor): an utterance is done once its history holds that many entries (<sos> included)."""
+    i32 = dict(dtype=torch.int32, device=device)
+    scores = torch.full((N, B), -1e10, dtype=torch.float32, device=device)
+    scores[:, 0] = 0.0
+    tokens = torch.full((N, B, Tmax), sos_id, **i32)
+    ind = torch.zeros((N, B, Tmax), **i32)
+    ind[:, :, 0] = torch.arange(B, **i32)[None, :]
+    conf = torch.zeros((N, B, Tmax), dtype=torch.float32, device=device)
+    ms = torch.as_tensor(max_steps, dtype=torch.int32).to(device).contiguous()
+    assert ms.numel() == N
+    return BeamState(scores=scores, finished=torch.zeros((N, B), **i32), step=torch.ones((N,), **i32), max_steps=ms, done=torch.zeros((N,), **i32),
+                     tokens=(tokens, tokens.clone()), ind=(ind, ind.clone()), conf=(conf, conf.clone()), beam_idx=torch.zeros((N, B), **i32),
+                     new_tokens=torch.zeros((N, B), **i32), new_conf=torch.zeros((N, B), dtype=torch.float32, device=device))
+
+
+def beam_step(logits: torch.Tensor, st: BeamState, *, eos_id: int, softmax_smoothing: float = 1.25, eos_penalty: float = 1.0) -> BeamState:
+    """One step of FireRedASR2's beam search for every utterance that is not done (``mi355_beam_step``): ``logits`` [N * B, V] (row stride >= V) ->
+    the state advanced in place (scores, finished, step, done, beam_idx, new_tokens, new_conf) and the histories written to the other buffer of each
+    pair.  Ties: the lower beam first, then the lower token id."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.float32 and logits.is_cuda
+    N, B = st.scores.shape
+    Tmax = st.tokens[0].shape[2]
+    assert logits.shape[0] == N * B
+    V = logits.shape[1]
+    src, dst = st.cur, 1 - st.cur
+    _lib.call_struct("mi355_beam_step", "mi355_beam_step_args", _stream(), logits=_ptr(logits), ld=logits.stride(0) if N * B > 1 else max(logits.stride(0), V),
+                     N=N, B=B, V=V, Tmax=Tmax, eos_id=eos_id, softmax_smoothing=softmax_smoothing, eos_penalty=eos_penalty, scores=_ptr(st.scores),
+                     finished=_ptr(st.finished), step=_ptr(st.step), max_steps=_ptr(st.max_steps), done=_ptr(st.done), tokens_in=_ptr(st.tokens[src]),
+                     tokens_out=_ptr(st.tokens[dst]), ind_in=_ptr(st.ind[src]), ind_out=_ptr(st.ind[dst]), conf_in=_ptr(st.conf[src]),
+                     conf_out=_ptr(st.conf[dst]), beam_idx=_ptr(st.beam_idx), new_tokens=_ptr(st.new_tokens), new_conf=_ptr(st.new_conf))
+    st.cur = dst
+    return st
+
+
+def beam_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ind: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, *, beams: int, heads: int,
+                   dh: int, scale: Optional[float] = None, Tk: Optional[int] = None):
+    """Decoder self-attention of one query per (utterance, beam) over a cache that is never re-gathered (``mi355_beam_attention``): ``q`` / ``out``
+    [N * B, heads * dh], ``k`` / ``v`` [N * B, Tcap, heads * dh] (row ``s`` of slot ``n * B + i`` = position ``s`` as beam ``i`` wrote it), ``ind`` int32
+    [N, B, Tmax] the slot of every position per beam (``beam_step`` maintains it), ``pos`` int32 [N] the last position to attend to (negative: a zero
+    row).  ``Tk`` (default: the caches' rows) bounds the positions read."""
+    assert q.dim() == 2 and out.dim() == 2 and q.stride(1) == 1 and out.stride(1) == 1 and q.dtype == torch.float32 and out.dtype == torch.float32
+    NB = q.shape[0]
+    _, Tcap, C, kss, ldk = _nlc(k)
+    _, Tv, Cv, vss, ldv = _nlc(v)
+    assert NB % beams == 0 and k.shape[0] == NB and v.shape[0] == NB and Tv == Tcap and C == heads * dh == Cv == q.shape[1] == out.shape[1] and out.shape[0] == NB
+    N = NB // beams
+    assert ind.dtype == torch.int32 and ind.is_cuda and ind.is_contiguous() and ind.dim() == 3 and tuple(ind.shape[:2]) == (N, beams)
+    assert pos.dtype == torch.int32 and pos.is_cuda and pos.is_contiguous() and pos.numel() == N and q.is_cuda and out.is_cuda
+    Tk = Tcap if Tk is None else Tk
+    assert 1 <= Tk <= Tcap
+    one = lambda t, s: s if t.shape[0] > 1 else max(s, t.shape[1])
+    _lib.call_struct("mi355_beam_attention", "mi355_beam_attention_args", _stream(), q=_ptr(q), ldq=one(q, q.stride(0)), k=_ptr(k),
+                     k_sstride=kss if NB > 1 else max(kss, Tcap * ldk), ldk=ldk, v=_ptr(v), v_sstride=vss if NB > 1 else max(vss, Tcap * ldv), ldv=ldv,
+                     ind=_ptr(ind), ld_ind=ind.shape[2], pos=_ptr(pos), N=N, B=beams, Tk=Tk, heads=heads, dh=dh,
+                     scale=(1.0 / math.sqrt(dh)) if scale is None else scale, out=_ptr(out), ldo=one(out, out.stride(0)))
+    return out
