@@ -1620,6 +1620,71 @@ typedef struct {
 } mi355_beam_attention_args;
 int mi355_beam_attention(const mi355_beam_attention_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Granite Speech NAR (stt/models/granite_speech_nar): block-local attention with Shaw relative positions, the self-conditioning softmax rows,
+ * the posterior-weighted pooling and the projector's window assembly (granite_nar.hip).  Four entry points added to ABI 37 (new structs and
+ * functions only; no existing layout changed).  Plain float32, no atomics, nothing allocated; every sum runs in a fixed order that depends on
+ * neither the launch geometry, nor the batch size, nor the other items' lengths: two calls on the same bytes give the same bits, and an item
+ * inside a ragged batch is bit-equal to that item alone.  lens [B] (device, nullable => T) is clamped to [0, T]; memory at and beyond lens[b]
+ * is never read.  A call that is refused (MI355_ERR_ARG / MI355_ERR_UNSUPPORTED) launches nothing and leaves every output untouched.
+ * ------------------------------------------------------------------------------------------ */
+/* ConformerAttention.__call__ behind its projections (encoder.py:97-126).  Head h sits at columns [h dh, (h + 1) dh) of every row; the
+ * tensors are NOT padded to a multiple of ctx.  With n = lens[b], for a query i < n of block m = i / ctx:
+ *   s_ij = scale * ( q_i . k_j + q_i . table[max_pos + (i - j)] ),   out_i = sum_{m ctx <= j < (m + 1) ctx} softmax_j(s_i.) v_j,
+ * where every key n <= j < (m + 1) ctx of that range is a ZERO key with a zero value that is NOT masked: its logit is the position term alone
+ * and it takes softmax mass (the reference zero-pads the last block and to_kv has no bias).  Output rows n <= i < T are written as zeros.
+ * table is [rows = 2 max_pos + 1, ldt >= dh], one table for all heads, row max_pos + d holding distance d = i - j, read in its own row order.
+ * dh 64 or 128 (else MI355_ERR_UNSUPPORTED); ctx >= 1, max_pos >= ctx - 1 and rows == 2 max_pos + 1, else MI355_ERR_ARG.  Rows 16-byte
+ * aligned (strides multiples of 4).  No [ctx, ctx] matrix is written to memory and there is no workspace. */
+typedef struct {
+  const float* q; int64_t q_bstride; int32_t ldq;        /* [B, T, ldq] */
+  const float* k; int64_t k_bstride; int32_t ldk;
+  const float* v; int64_t v_bstride; int32_t ldv;
+  const float* table; int32_t ldt; int32_t rows; int32_t max_pos;   /* [rows, ldt] */
+  const int32_t* lens; int32_t B; int32_t T; int32_t heads; int32_t dh; int32_t ctx; float scale;
+  float* out; int64_t out_bstride; int32_t ldo;          /* [B, T, ldo] */
+} mi355_shaw_block_attention_args;
+int mi355_shaw_block_attention(const mi355_shaw_block_attention_args* a, void* stream);
+
+#define MI355_SELFCOND_WAVE_MAX_V 256   /* up to here one wave owns a row (four rows per workgroup); above, one workgroup */
+/* The self-conditioning step of ConformerEncoder.__call__ (encoder.py:280-281) per row of logits [rows, ld >= V], any V >= 1:
+ *   probs[r, c] = expf(x_c - max) / sum_c expf(x_c - max),   p_blank[r] = probs[r, 0].
+ * The maximum is exact; the sum is per thread over its columns t, t + NT, ... ascending (NT = 64 or 256 by V alone), then the wave butterfly
+ * and, for NT = 256, (w0 + w1) + (w2 + w3).  Finite logits are the caller's contract. */
+typedef struct {
+  const float* logits; int64_t ld; int64_t rows; int32_t V;
+  float* probs; int64_t ld_probs;                        /* [rows, ld_probs >= V] */
+  float* p_blank;                                        /* [rows] */
+} mi355_selfcond_rows_args;
+int mi355_selfcond_rows(const mi355_selfcond_rows_args* a, void* stream);
+
+/* _posterior_weighted_pool (encoder.py:302-334): out [B, ceil(T / window), ldo >= C].  With w_t = 1 - p_blank[b, t] for t < lens[b] and 0
+ * beyond, per window n of frames n window .. min((n + 1) window, T) - 1:
+ *   out[b, n, c] = sum_t h[b, t, c] * ( w_t / max(sum_t w_t, 1e-6) ),
+ * the weights' sum in ascending order, the pooled value an fmaf chain from zero over t ascending.  A partial last window weights only its
+ * real frames; a window wholly at or beyond lens[b] comes back zero. */
+typedef struct {
+  const float* h; int64_t h_bstride; int32_t ldh;        /* [B, T, ldh] */
+  const float* p_blank; int64_t pb_bstride;              /* [B, T] */
+  int32_t window; const int32_t* lens; int32_t B; int32_t T; int32_t C;
+  float* out; int64_t out_bstride; int32_t ldo;          /* [B, ceil(T / window), ldo] */
+} mi355_posterior_pool_args;
+int mi355_posterior_pool(const mi355_posterior_pool_args* a, void* stream);
+
+/* The window assembly of the projector (projector.py:190-215) in one launch, nblocks = ceil(T / block), nq = block / rate.  Row r of window
+ * n of item b is h[b, n block + r] where that frame is below lens[b] and ZERO otherwise (the reference's right padding, before any add):
+ *   kv[b nblocks + n, r, c]      = row_r[c] + positions[r, c]
+ *   queries[b nblocks + n, g, c] = query[g, c] + ( sum_{i < rate} row_{g rate + i}[c] ) / rate        (the sum in ascending order)
+ * query [nq, C], positions [block, C], queries [B nblocks, nq, C] and kv [B nblocks, block, C] are contiguous.  block a positive multiple of
+ * rate, else MI355_ERR_ARG. */
+typedef struct {
+  const float* h; int64_t h_bstride; int32_t ldh;        /* [B, T, ldh] */
+  const int32_t* lens; int32_t B; int32_t T; int32_t C; int32_t block; int32_t rate;
+  const float* query; const float* positions;            /* [block / rate, C]; [block, C] */
+  float* queries; float* kv;                             /* [B nblocks, block / rate, C]; [B nblocks, block, C] */
+} mi355_qformer_windows_args;
+int mi355_qformer_windows(const mi355_qformer_windows_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmi355audio.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "mi355audio.h")
 SOURCES = ["api.cpp", "conv_gemm.hip", "conv_ws4.hip", "conv_ws4_p4.hip", "conv_ws4_p13.hip", "conv_ws4_p5.hip", "conv_ws4_p6.hip", "conv_ws4_p5_probe.hip", "conv_ws4_fq.hip", "upsample_poly.hip", "conv_quant.hip", "norm.hip", "group_norm.hip", "s3.hip", "conformer.hip", "narrow_attn.hip", "mid_attn.hip", "align.hip", "lstm.hip", "lstm_seq.hip", "gru.hip", "dfn.hip", "bandsplit.hip", "sanm.hip", "mossformer.hip", "attention.hip", "glue.hip", "source.hip", "fft.hip", "flash_attn.hip",
-           "decode_rules.hip", "gemv.hip", "gemv_mfma.hip", "gemv_mfma_fp8.hip", "gemm_rows.hip", "rows_pipe.hip", "transformer.hip", "rvq.hip", "ecapa.hip", "sampler.hip", "stack_step.cpp", "firered.hip"]
+           "decode_rules.hip", "gemv.hip", "gemv_mfma.hip", "gemv_mfma_fp8.hip", "gemm_rows.hip", "rows_pipe.hip", "transformer.hip", "rvq.hip", "ecapa.hip", "sampler.hip", "stack_step.cpp", "firered.hip", "granite_nar.hip"]
 # per-file extra flags: source.hip and dfn.hip mirror the reference's fp32 op order one rounding at a time
 EXTRA_FLAGS = {"source.hip": ["-ffp-contract=off"], "dfn.hip": ["-ffp-contract=off"]}
 # Every translation unit: no SLP vectorisation.  Under plain -O3 hipcc packs adjacent scalar fp32 adds / multiplies into v_pk_add_f32 / v_pk_mul_f32 /

@@ -2080,3 +2080,91 @@ def beam_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ind: torch
                      ind=_ptr(ind), ld_ind=ind.shape[2], pos=_ptr(pos), N=N, B=beams, Tk=Tk, heads=heads, dh=dh,
                      scale=(1.0 / math.sqrt(dh)) if scale is None else scale, out=_ptr(out), ldo=one(out, out.stride(0)))
     return out
+
+
+# --------------------------------------------------------------------------------------- Granite Speech NAR (granite_nar.hip)
+SELFCOND_WAVE_MAX_V = 256   # MI355_SELFCOND_WAVE_MAX_V
+
+
+def shaw_block_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, table: torch.Tensor, out: torch.Tensor, *, heads: int, dh: int, ctx: int,
+                         max_pos: int, scale: Optional[float] = None, lens: Optional[torch.Tensor] = None, check_lens: bool = True):
+    """``out_i = sum_j softmax_j(scale (q_i . k_j + q_i . table[max_pos + i - j])) v_j`` over the ``ctx`` keys of query ``i``'s own block
+    ``[m ctx, (m + 1) ctx)``, ``m = i // ctx`` (``mi355_shaw_block_attention``): Granite Speech NAR's block-local attention with Shaw relative
+    positions behind its projections.  ``q`` / ``k`` / ``v`` / ``out`` channels-last views [B, T, heads * dh] (thirds of a fused buffer or contiguous),
+    NOT padded to a multiple of ``ctx``; ``table`` [2 max_pos + 1, dh], one for all heads, row ``max_pos + d`` holding distance ``d = i - j``.  A key
+    of the block at or beyond ``lens[b]`` counts as a zero key with a zero value and is NOT masked (the reference's zero padding of the last block);
+    rows at and beyond ``lens[b]`` come back zero.  Every ``lens[b]`` must be in ``[0, T]``: checked here with one device read of ``lens``, which a
+    caller that built ``lens`` from host integers it has already checked turns off (``check_lens=False``)."""
+    B, T, C, qbs, ldq = _nlc(q)
+    Bk, Tk, Ck, kbs, ldk = _nlc(k)
+    Bv, Tv, Cv, vbs, ldv = _nlc(v)
+    Bo, To, Co, obs, ldo = _nlc(out)
+    hd = heads * dh
+    assert (Bk, Tk) == (B, T) and (Bv, Tv) == (B, T) and (Bo, To) == (B, T) and min(C, Ck, Cv, Co) >= hd
+    assert table.dim() == 2 and table.stride(1) == 1 and table.shape[1] >= dh and table.dtype == torch.float32 and table.is_cuda
+    lp = _lens_arg(lens, B)
+    if lens is not None and check_lens:
+        lo, hi = int(lens.min()), int(lens.max())
+        if lo < 0 or hi > T:
+            raise _lib.Mi355Error(f"shaw_block_attention: lens must lie in [0, T = {T}] (got min {lo}, max {hi})")
+    _lib.call_struct("mi355_shaw_block_attention", "mi355_shaw_block_attention_args", _stream(), q=_ptr(q), q_bstride=qbs, ldq=ldq, k=_ptr(k),
+                     k_bstride=kbs, ldk=ldk, v=_ptr(v), v_bstride=vbs, ldv=ldv, table=_ptr(table), ldt=table.stride(0), rows=table.shape[0],
+                     max_pos=max_pos, lens=lp, B=B, T=T, heads=heads, dh=dh, ctx=ctx, scale=dh ** -0.5 if scale is None else scale, out=_ptr(out),
+                     out_bstride=obs, ldo=ldo)
+    return out
+
+
+def selfcond_rows(logits: torch.Tensor, *, probs: Optional[torch.Tensor] = None, p_blank: Optional[torch.Tensor] = None):
+    """Per row of ``logits`` [rows, V] (row stride >= V): ``(probs [rows, V], p_blank [rows])`` -- the float32 softmax probabilities and column 0
+    of them (``mi355_selfcond_rows``): the self-conditioning step of Granite Speech NAR's encoder.  One wave per row up to
+    ``SELFCOND_WAVE_MAX_V`` columns, one workgroup above."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.float32 and logits.is_cuda
+    rows, V = logits.shape
+    dev = logits.device
+    probs = torch.empty((rows, V), dtype=torch.float32, device=dev) if probs is None else probs
+    p_blank = torch.empty((rows,), dtype=torch.float32, device=dev) if p_blank is None else p_blank
+    assert probs.shape == logits.shape and probs.stride(1) == 1 and probs.dtype == torch.float32 and probs.is_cuda
+    assert p_blank.dtype == torch.float32 and p_blank.is_cuda and p_blank.is_contiguous() and p_blank.numel() == rows
+    one = lambda t: t.stride(0) if rows > 1 else max(t.stride(0), V)
+    _lib.call_struct("mi355_selfcond_rows", "mi355_selfcond_rows_args", _stream(), logits=_ptr(logits), ld=one(logits), rows=rows, V=V, probs=_ptr(probs),
+                     ld_probs=one(probs), p_blank=_ptr(p_blank))
+    return probs, p_blank
+
+
+def posterior_pool(h: torch.Tensor, p_blank: torch.Tensor, window: int, *, lens: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """``_posterior_weighted_pool`` of Granite Speech NAR's encoder (``mi355_posterior_pool``): ``h`` [B, T, C], ``p_blank`` [B, T] ->
+    [B, ceil(T / window), C], every window's frames weighted by ``(1 - p_blank) / max(sum, 1e-6)``.  Frames at and beyond ``lens[b]`` weigh 0 (a
+    partial last window weights only its real frames); a window wholly beyond the item comes back zero."""
+    B, T, C, hbs, ldh = _nlc(h)
+    assert p_blank.dim() == 2 and tuple(p_blank.shape) == (B, T) and p_blank.stride(1) == 1 and p_blank.dtype == torch.float32 and p_blank.is_cuda
+    nw = (T + window - 1) // window if window >= 1 else 1
+    if out is None:
+        out = torch.empty((B, nw, C), dtype=torch.float32, device=h.device)
+    Bo, No, Co, obs, ldo = _nlc(out)
+    assert (Bo, No, Co) == (B, nw, C)
+    _lib.call_struct("mi355_posterior_pool", "mi355_posterior_pool_args", _stream(), h=_ptr(h), h_bstride=hbs, ldh=ldh, p_blank=_ptr(p_blank),
+                     pb_bstride=p_blank.stride(0) if B > 1 else max(p_blank.stride(0), T), window=window, lens=_lens_arg(lens, B), B=B, T=T, C=C,
+                     out=_ptr(out), out_bstride=obs, ldo=ldo)
+    return out
+
+
+def qformer_windows(h: torch.Tensor, query: torch.Tensor, positions: torch.Tensor, *, block: int, rate: int, lens: Optional[torch.Tensor] = None,
+                    queries: Optional[torch.Tensor] = None, kv: Optional[torch.Tensor] = None):
+    """The window assembly of Granite Speech NAR's projector in one launch (``mi355_qformer_windows``): ``h`` [B, T, C] ->
+    ``(queries [B nblocks, block / rate, C], kv [B nblocks, block, C])`` with ``nblocks = ceil(T / block)``.  Every window is right-padded with
+    zero rows from ``lens[b]`` on; ``queries`` = ``query`` [block / rate, C] + the mean over each group of ``rate`` rows, ``kv`` = the window +
+    ``positions`` [block, C]."""
+    B, T, C, hbs, ldh = _nlc(h)
+    if block < 1 or rate < 1 or block % rate:
+        raise _lib.Mi355Error(f"qformer_windows: block = {block} must be a positive multiple of rate = {rate}")
+    nq, nb = block // rate, (T + block - 1) // block
+    f32 = lambda t, shape: t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape
+    assert f32(query, (nq, C)) and f32(positions, (block, C))
+    if queries is None:
+        queries = torch.empty((B * nb, nq, C), dtype=torch.float32, device=h.device)
+    if kv is None:
+        kv = torch.empty((B * nb, block, C), dtype=torch.float32, device=h.device)
+    assert f32(queries, (B * nb, nq, C)) and f32(kv, (B * nb, block, C))
+    _lib.call_struct("mi355_qformer_windows", "mi355_qformer_windows_args", _stream(), h=_ptr(h), h_bstride=hbs, ldh=ldh, lens=_lens_arg(lens, B), B=B, T=T,
+                     C=C, block=block, rate=rate, query=_ptr(query), positions=_ptr(positions), queries=_ptr(queries), kv=_ptr(kv))
+    return queries, kv
