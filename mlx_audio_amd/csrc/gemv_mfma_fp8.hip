@@ -1,64 +1,45 @@
-// Skinny GEMM for 5..8 rows per decode step with fp8 weight images on the fp8 matrix pipe (gfx950): y[m, n] = epilogue(sum_k norm(x)[m, k] * W[n, k]).
+// Skinny GEMM for 5..8 rows per decode step with fp8 weight images on the matrix pipe (gfx950): y[m, n] = epilogue(sum_k norm(x)[m, k] * W[n, k]).
 //
 // BASELINE.json config[4] asks for fp8 GEMMs on CSM; mi355_pack_rowmajor_fp8_host gives every Linear an OCP e4m3fn byte image with one power-of-two
-// scale per output row.  The FMA kernel (gemv.hip) decodes those bytes to fp32 and spends 8 FMAs per weight element at 8 rows; here the bytes go
-// to v_mfma_f32_16x16x32_fp8_fp8 untouched:
+// scale per output row.  The FMA kernel (gemv.hip) decodes those bytes to fp32 and spends 8 FMAs per weight element at 8 rows; here the weight
+// stream stays one byte per element and the products go to the matrix pipe:
 //   * A operand = a 16-row tile of W straight from HBM: lane (i = lane & 15, g = lane >> 4) loads the 16 contiguous bytes W[n0 + i][k0 + 16 g .. + 16)
-//     of a 64-wide k step and feeds its two 8-byte halves to two MFMAs (the contraction index is a free relabelling as long as A and B agree);
-//   * B operand = the (normalised) input rows.  fp8 has 4 significant bits, so a row is scaled by a power of two into [-240, 240] and split into
-//     NT = 4 e4m3 TERMS of decreasing weight: x / s = h0 + h1 / 16 + h2 / 256 + h3 / 4096 (each remainder is exact in fp32 and is re-scaled by 16 before
-//     it is rounded again), ~16 significant bits in total -- the accuracy of the bf16 hi + lo split the 16-bit kernel uses.  Each term has its own
-//     accumulator (the terms differ by a power of two that cannot ride inside an e4m3 operand); they are combined per 2048-column chunk together with
-//     the chunk's row scale of x, and the row scale of W is applied in the epilogue.  The images live in LDS in fragment order [term][k step][half][group][row] x 8 bytes;
-//   * split-K over the four waves of a workgroup and fused LayerNorm / RMSNorm exactly as gemv_mfma.hip; the epilogue is linear_common.h's.
+//     of a 64-wide k step; each 8-byte half is decoded to eight bf16 values in registers (exact: 4 significant bits, bf16's exponent range covers
+//     e4m3's -- the conversion the rows pipeline uses) and feeds v_mfma_f32_16x16x32_bf16;
+//   * B operand = the (normalised) input rows as hi + lo bf16 images (split_hi_lo of linear_common.h: ~16 mantissa bits, the split of gemv_mfma.hip)
+//     in LDS in fragment order [image][k step][half][group][row] x 16 bytes.
+//     (Not v_mfma_f32_16x16x32_fp8_fp8: it drops products 2^14 below the largest of their 64-bit operand -- docs/HISTORY.md.)
+//   * split-K over the four waves of a workgroup and fused LayerNorm / RMSNorm exactly as gemv_mfma.hip; the row scale of W is applied in the
+//     epilogue, which is linear_common.h's.
 // Same contract as the 16-bit matrix-pipe kernel (5..8 rows, K % 64 == 0; a fused norm needs K <= 2048); MI355_GEMV_MFMA_FP8=0 keeps the FMA kernel.
 #include <stdlib.h>
 #include "linear_common.h"
 
 namespace {
 
-constexpr int kKC8 = 2048;  // input columns staged: 4 terms x 8 rows x 1 byte x kKC8 = 64 KB of LDS
+constexpr int kKC8 = 2048;  // input columns staged: 2 images x 8 rows x 2 bytes x kKC8 = 64 KB of LDS
 constexpr int kD8 = 8;      // weight prefetch depth in k steps (16 bytes per lane and step)
-constexpr int NT = 4;       // e4m3 terms of the input rows
 
-// 8 fp32 values -> NT e4m3 terms (8 bytes each); the values are already scaled into the e4m3 range
-__device__ __forceinline__ void split_fp8(float (&v)[8], uint2 (&out)[NT]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-    out[t] = make_uint2((uint32_t)lo, (uint32_t)hi);
-    if (t + 1 < NT) {
-      v[0] = (v[0] - __builtin_amdgcn_cvt_f32_fp8(lo, 0)) * 16.f; v[1] = (v[1] - __builtin_amdgcn_cvt_f32_fp8(lo, 1)) * 16.f;
-      v[2] = (v[2] - __builtin_amdgcn_cvt_f32_fp8(lo, 2)) * 16.f; v[3] = (v[3] - __builtin_amdgcn_cvt_f32_fp8(lo, 3)) * 16.f;
-      v[4] = (v[4] - __builtin_amdgcn_cvt_f32_fp8(hi, 0)) * 16.f; v[5] = (v[5] - __builtin_amdgcn_cvt_f32_fp8(hi, 1)) * 16.f;
-      v[6] = (v[6] - __builtin_amdgcn_cvt_f32_fp8(hi, 2)) * 16.f; v[7] = (v[7] - __builtin_amdgcn_cvt_f32_fp8(hi, 3)) * 16.f;
-    }
-  }
+// eight OCP e4m3fn bytes -> eight bf16 values (exact)
+__device__ __forceinline__ uint4 fp8x8_to_bf16x8(const uint32_t lo, const uint32_t hi) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+  return make_uint4(pack_bf16x2(a[0], a[1]), pack_bf16x2(b[0], b[1]), pack_bf16x2(c[0], c[1]), pack_bf16x2(d[0], d[1]));
 }
 
-__device__ __forceinline__ f32x4 mfma_fp8(const uint2 a, const uint2 b, const f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(__builtin_bit_cast(long, a), __builtin_bit_cast(long, b), c, 0, 0, 0);
-}
-
-// TPW column tiles per workgroup (grid-stride: tile = blockIdx.x + j * gridDim.x) and a chunk loop over K: the split of the input rows into e4m3
-// terms -- ~2.5 k VALU instructions per thread, the dominant cost of the first version, in which every one of the N / 16 workgroups of a launch
-// repeated it -- is done once per 2048-column chunk per WORKGROUP and amortised over its TPW tiles; K > 2048 (the down projections) walks the
-// chunks with the next (tile, chunk) segment's weights already in flight.  Each chunk carries its own power-of-two row scales, so a segment's
-// term accumulators are folded into a float total right away.
+// TPW column tiles per workgroup (grid-stride: tile = blockIdx.x + j * gridDim.x) and a chunk loop over K: the staging of the input rows (norm,
+// hi + lo split) is done once per 2048-column chunk per WORKGROUP and amortised over its TPW tiles; K > 2048 (the down projections) walks the
+// chunks with the next (tile, chunk) segment's weights already in flight.
 template <int TPW>
 __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_args a, const int ntiles) {
-  extern __shared__ __attribute__((aligned(16))) uint2 planes[];  // [NT][32 steps][2 halves][4 groups][8 rows] 8-byte pieces of ONE chunk
+  extern __shared__ __attribute__((aligned(16))) uint4 planes[];  // [2 images][32 steps][2 halves][4 groups][8 rows] 16-byte pieces of ONE chunk
   __shared__ float red[4][256];
   __shared__ float st_part[4][8];
-  __shared__ float st_val[8];     // the chunk's power-of-two scale per row
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, M = a.M;
   const int nch = (K + kKC8 - 1) / kKC8;
-  constexpr int img = (kKC8 / 64) * 64;        // 8-byte pieces per term image of a chunk
+  constexpr int img = (kKC8 / 64) * 64;        // 16-byte pieces per image of a chunk
   const int gi = lane >> 4, li = lane & 15;
   const uint8_t* wrow[TPW];
 #pragma unroll
@@ -112,9 +93,9 @@ __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_arg
           xb[m] = *(const float4*)(p + 4);
         }
       }
-      auto block_rows = [&](float (&s)[8], bool is_max) {   // per-row reduction of s[m] over the workgroup -> s[m] (sum or max)
+      auto block_rows = [&](float (&s)[8]) {   // per-row sum of s[m] over the workgroup -> s[m]
 #pragma unroll
-        for (int m = 0; m < 8; ++m) s[m] = is_max ? wave_max(s[m]) : wave_sum(s[m]);
+        for (int m = 0; m < 8; ++m) s[m] = wave_sum(s[m]);
         if (lane < 8) {
           float v = s[0];
 #pragma unroll
@@ -123,16 +104,14 @@ __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_arg
         }
         __syncthreads();
 #pragma unroll
-        for (int m = 0; m < 8; ++m)
-          s[m] = is_max ? fmaxf(fmaxf(st_part[0][m], st_part[1][m]), fmaxf(st_part[2][m], st_part[3][m]))
-                        : (st_part[0][m] + st_part[1][m]) + (st_part[2][m] + st_part[3][m]);
+        for (int m = 0; m < 8; ++m) s[m] = (st_part[0][m] + st_part[1][m]) + (st_part[2][m] + st_part[3][m]);
         __syncthreads();
       };
       if (a.norm) {  // (eligibility: a fused norm implies K <= 2048, one chunk) two-pass statistics from the registers, then the affine part
         float s[8], mean[8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) s[m] = ((xa[m].x + xa[m].y) + (xa[m].z + xa[m].w)) + ((xb[m].x + xb[m].y) + (xb[m].z + xb[m].w));
-        block_rows(s, false);
+        block_rows(s);
 #pragma unroll
         for (int m = 0; m < 8; ++m) mean[m] = a.norm == 1 ? s[m] / (float)K : 0.f;
 #pragma unroll
@@ -145,7 +124,7 @@ __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_arg
           }
           s[m] = qv;
         }
-        block_rows(s, false);
+        block_rows(s);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
           const float var = s[m] / (float)K;
@@ -157,40 +136,22 @@ __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_arg
                               (xb[m].w - mu) * rs * wb.w + bb.w);
         }
       }
-      // per-row power-of-two scale of this chunk into [-240, 240]: s = 2^ceil(log2(amax / 240))
-      float amax[8];
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        amax[m] = 0.f;
-        if (on) amax[m] = fmaxf(fmaxf(fmaxf(fabsf(xa[m].x), fabsf(xa[m].y)), fmaxf(fabsf(xa[m].z), fabsf(xa[m].w))),
-                                fmaxf(fmaxf(fabsf(xb[m].x), fabsf(xb[m].y)), fmaxf(fabsf(xb[m].z), fabsf(xb[m].w))));
-      }
-      block_rows(amax, true);
-      float inv_s[8];
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        int e = 0;
-        const float mant = frexpf(amax[m] * (1.0f / 240.0f), &e);   // amax / 240 = mant * 2^e, mant in [0.5, 1)
-        const int se = amax[m] > 0.f ? (mant == 0.5f ? e - 1 : e) : 0;
-        inv_s[m] = ldexpf(1.0f, -se);
-        if (tid == 0) st_val[m] = ldexpf(1.0f, se);
-      }
-      if (on) {
+      if (on) {   // hi / lo images in fragment order: piece (step, half, group, row) = ((step * 2 + half) * 4 + group) * 8 + row
         const int step = q >> 3, r = q & 7, g = r >> 1, h = r & 1;
         const int base = ((step * 2 + h) * 4 + g) * 8;
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-          float v[8] = {xa[m].x * inv_s[m], xa[m].y * inv_s[m], xa[m].z * inv_s[m], xa[m].w * inv_s[m],
-                        xb[m].x * inv_s[m], xb[m].y * inv_s[m], xb[m].z * inv_s[m], xb[m].w * inv_s[m]};
-          uint2 terms[NT];
-          split_fp8(v, terms);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) planes[t * img + base + m] = terms[t];
+          uint4 hi, lo;
+          split_hi_lo<false>(xa[m].x, xa[m].y, hi.x, lo.x);
+          split_hi_lo<false>(xa[m].z, xa[m].w, hi.y, lo.y);
+          split_hi_lo<false>(xb[m].x, xb[m].y, hi.z, lo.z);
+          split_hi_lo<false>(xb[m].z, xb[m].w, hi.w, lo.w);
+          planes[base + m] = hi;
+          planes[img + base + m] = lo;
         }
       }
     }
     __syncthreads();
-    const float xs = st_val[li & 7];   // this lane's D column is input row li (rows >= 8 alias li & 7: never stored)
     // ---- the TPW tiles of this workgroup against chunk c
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
@@ -198,29 +159,19 @@ __global__ __launch_bounds__(256) void gemv_mfma_fp8_kernel(const mi355_gemv_arg
       for (int d = 0; d < kD8; ++d) cur[d] = nxt[d];
       if (j + 1 < TPW) issue_seg(c, j + 1, nxt);
       else if (c + 1 < nch) issue_seg(c + 1, 0, nxt);
-      f32x4 acc[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int d = 0; d < kD8; ++d) {
         const int sl = wave + 4 * d;
         if (sl < steps_c) {
-          const uint2 w0 = make_uint2(cur[d].x, cur[d].y), w1 = make_uint2(cur[d].z, cur[d].w);
-          const int p0 = ((sl * 2 + 0) * 4 + gi) * 8 + (li & 7);
+          const uint4 w0 = fp8x8_to_bf16x8(cur[d].x, cur[d].y), w1 = fp8x8_to_bf16x8(cur[d].z, cur[d].w);
+          const int p0 = ((sl * 2 + 0) * 4 + gi) * 8 + (li & 7);   // this lane's D column is input row li (rows >= 8 alias li & 7: never stored)
           const int p1 = ((sl * 2 + 1) * 4 + gi) * 8 + (li & 7);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) {
-            acc[t] = mfma_fp8(w0, planes[t * img + p0], acc[t]);
-            acc[t] = mfma_fp8(w1, planes[t * img + p1], acc[t]);
-          }
+          const uint4 h0 = planes[p0], h1 = planes[p1], l0 = planes[img + p0], l1 = planes[img + p1];
+          tot[j] = mfma_16x16x32<false>(w0, h0, tot[j]);
+          tot[j] = mfma_16x16x32<false>(w1, h1, tot[j]);
+          tot[j] = mfma_16x16x32<false>(w0, l0, tot[j]);
+          tot[j] = mfma_16x16x32<false>(w1, l1, tot[j]);
         }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {   // x / s = h0 + h1 / 16 + h2 / 256 + h3 / 4096
-        float v = acc[NT - 1][r];
-#pragma unroll
-        for (int t = NT - 2; t >= 0; --t) v = v * (1.0f / 16.0f) + acc[t][r];
-        tot[j][r] += v * xs;
       }
     }
   }
@@ -261,7 +212,7 @@ int mi355_gemv_mfma_fp8_eligible(const mi355_gemv_args& a) {
 
 int mi355_gemv_mfma_fp8_launch(const mi355_gemv_args& a, hipStream_t st) {
   static bool attr_set = false;  // benign race: the attribute is idempotent
-  const size_t lds = (size_t)kKC8 * 8 * NT;   // NT terms x 32 steps x 64 pieces x 8 bytes (one chunk)
+  const size_t lds = (size_t)kKC8 * 32;   // 2 images x 32 steps x 64 pieces x 16 bytes (one chunk)
   if (!attr_set) {
     hipError_t e1 = hipFuncSetAttribute((const void*)gemv_mfma_fp8_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipError_t e2 = hipFuncSetAttribute((const void*)gemv_mfma_fp8_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

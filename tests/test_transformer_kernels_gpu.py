@@ -620,9 +620,9 @@ def test_gemv_fp8_weights(ops, M, N, K, act, use_res, glu):
     y = torch.empty(M, N // 2 if glu else N, device=DEV)
     ops.gemv(xd[:, :K], rw, y, post_act=act, res=None if res is None else res.to(DEV), glu=glu)
     torch.cuda.synchronize()
-    # 5..8 rows with K % 64 == 0 run on the fp8 matrix pipe (1, 2 or 4 column tiles per workgroup, 2048-column chunks of K): the input rows are split into four e4m3 terms (~16 significant bits, the
-    # accuracy of the bf16 hi + lo split: same bar as the 16-bit matrix-pipe kernel)
-    # (four e4m3 terms = ~16 significant bits of the input rows; a SwiGLU output multiplies two such results: 3e-5, the conv path's hi + lo bar)
+    # 5..8 rows with K % 64 == 0 run on the matrix pipe (1, 2 or 4 column tiles per workgroup, 2048-column chunks of K): the weight bytes are decoded to bf16 in registers and the input rows
+    # are split into hi + lo bf16 images (~16 significant bits: same bar as the 16-bit matrix-pipe kernel)
+    # (hi + lo = ~16 significant bits of the input rows; a SwiGLU output multiplies two such results: 3e-5, the conv path's hi + lo bar)
     tol = 3e-5 if (5 <= M <= 8 and K % 64 == 0) else 5e-6
     assert rel_err(y.cpu(), v) < tol, rel_err(y.cpu(), v)
 
