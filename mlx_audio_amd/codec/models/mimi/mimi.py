@@ -250,6 +250,9 @@ class MimiDecoder:
     def dequantize(self, codes: torch.Tensor) -> torch.Tensor:
         B, Q, N = codes.shape
         out = self._f(B, N, self.cfg.dimension)
+        # a code past the codebook (a CSM head has audio_vocab_size = bins + 3 columns and may emit one) has no entry: it is masked (id -1 adds
+        # nothing), once for all groups -- mi355_embed_sum has no row bound and would read past the end of the table
+        codes = codes.masked_fill(codes >= self.cfg.quantizer_bins, -1)
         q0 = 0
         for gi, (table, offs, proj, n) in enumerate(self.rvq):
             ids = codes[:, q0:q0 + n, :].permute(0, 2, 1)

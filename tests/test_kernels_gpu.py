@@ -54,7 +54,8 @@ def ref_conv_nlc(x, w, b, dil, pad):
     (128, 22, 7, 1, 500, 1, 0),
     # the wave-specialised producer / consumer kernel (tile code 6128128; +10000000 = consumers at default priority, +80000000 = one
     # workgroup per tile instead of persistent workgroups): conv mode with 1, 2 and 3 N-tiles, K = 1 / 2 / odd, dilation, ragged channel
-    # counts, more row tiles than XCDs ...
+    # counts, more row tiles than XCDs ...  (More tiles than persistent workgroups: tests/test_conv_kernel_edges_gpu.py::test_persistent_walk_small
+    # walks 9 .. 40 tiles on 8 / 16 workgroups at every precision instead of 547 tiles on 512.)
     (128, 128, 7, 3, 300, 2, 6128128),
     (128, 128, 3, 1, 1500, 3, 6128128),
     (256, 256, 11, 5, 257, 1, 6128128),
@@ -66,7 +67,6 @@ def ref_conv_nlc(x, w, b, dil, pad):
     (128, 128, 4, 2, 2100, 2, 16128128),
     (128, 128, 7, 3, 300, 2, 86128128),
     (256, 256, 11, 5, 1200, 3, 86128128),
-    (128, 128, 3, 1, 70000, 1, 6128128),
     # ... and GEMM mode (K = 1: 64-channel super-chunks; odd / ragged chunk counts, one row tile, many row tiles)
     (512, 64, 1, 1, 777, 3, 6128128),
     (160, 128, 1, 1, 2100, 1, 6128128),
@@ -96,7 +96,6 @@ def ref_conv_nlc(x, w, b, dil, pad):
     (64, 64, 1, 1, 130, 1, 6128064),
     (160, 40, 1, 1, 2100, 1, 16128064),
     (64, 64, 3, 1, 20000, 1, 0),
-    (64, 64, 3, 1, 70000, 1, 86128064),
 ])
 def test_conv_gemm_plain(ops, cin, cout, k, dil, L, B, tile):
     g = torch.Generator().manual_seed(cin + cout + k)

@@ -47,6 +47,30 @@ def test_tiny_stages_waveform_and_causality():
     assert float((got[..., :n] - part).abs().max()) <= 1e-4 * peak
 
 
+def test_codes_past_the_codebook_add_nothing():
+    """A CSM head is three columns wider than the Mimi codebooks (audio_vocab_size 2051 / 2048 bins; 67 / 64 in the tiny configs) and may emit a code
+    with no entry.  Such a code is masked, not looked up (the table ends there): with entry 5 of every codebook set to zero, codes >= bins decode bit
+    for bit like code 5, through the one-shot and the streaming decoder."""
+    from mlx_audio_amd.codec.models.mimi.mimi import tiny_mimi_config
+
+    cfg = tiny_mimi_config()
+    eng, _, M = _pair(cfg, 1)
+    bins = cfg.quantizer_bins
+    for table, _, _, n in eng.rvq:
+        for i in range(n):
+            table[i * bins + 5].zero_()
+    codes = M.make_codes(2, 9, cfg, seed=3)
+    inside = codes.clone()
+    for b, q, t, past in ((0, 0, 2, 0), (1, cfg.quantizer_nq - 1, 5, 2), (0, cfg.quantizer_nq - 1, 8, 1), (1, 1, 0, 1)):
+        codes[b, q, t], inside[b, q, t] = bins + past, 5
+    got, want = eng(codes), eng(inside)
+    st = eng.new_stream(2)
+    step = torch.cat([eng.decode_step(codes[..., t:t + 3], st) for t in range(0, 9, 3)], dim=-1)
+    torch.cuda.synchronize()
+    assert torch.equal(got, want)
+    assert float((step - want).abs().max()) <= 1e-4 * float(want.abs().max())
+
+
 def test_mimi_202407_reference_shape_pin_and_values():
     from mlx_audio_amd.codec.models.mimi.mimi import mimi_202407
 
