@@ -122,7 +122,8 @@ typedef struct {
                               lo pass costs ~0.27 of a 16-bit pass instead of ~0.55), the lo planes in LDS and the lo weight stream
                               halve; ~13 significant bits of the activation (waveform: ~4e-4 of the peak, 70 dB, against the 2e-3 /
                               50 dB bars: profiles/r6_split_format_study_fp6.txt).  Same eligibility and fallback as 5 */
-  int32_t tile;        /* 0 = auto, else BM*1000+BN (128128, 64128, 64064), 6128128 / 7128128 = wave-specialised 8-wave kernels (ws4 / ws3),
+  int32_t tile;        /* 0 = auto, else BM*1000+BN (128128, 64128, 64064), 6128128 / 6128064 (+ 10000000 * feature bits, + 100000000 *
+                          ablation build) = the wave-specialised 8-wave kernel (ws4) on 128 x 128 / 128 x 64 tiles,
                           2064128 / 2064064 (+ 10000000 * groups) = split-K on 64-row tiles (needs split_ws) */
   /* optional instance-norm statistics of the STORED output, fused into the epilogue (plain stores only): per block of
      MI355_STATS_ROWS output rows and per channel the pair (sum, sum of squared deviations from the block mean), written
@@ -168,6 +169,42 @@ typedef struct {
 #define MI355_STATS_ROWS 64
 
 int mi355_conv_gemm(const mi355_conv_gemm_args* a, void* stream);
+/* What mi355_conv_gemm decides for a launch before it launches anything (an additive entry point: the ABI version stays).  Fields that do not apply to the family are 0. */
+enum { MI355_ROUTE_4WAVE = 0, MI355_ROUTE_SPLITK = 1, MI355_ROUTE_WS4 = 2 };
+typedef struct {
+  int32_t family;        /* MI355_ROUTE_* */
+  int32_t precision;     /* the arithmetic actually run (1 .. 6) */
+  int32_t mx_fallback;   /* 1: an MX image (precision 5 / 6) on the precision-4 arithmetic of the 4-wave kernels */
+  int32_t mx_lo_slices;  /* ... whose kernels skip this many e4m3 / FP4 tap-pair slices per chunk of the image */
+  int32_t bm;
+  int32_t bn;            /* tile rows and columns */
+  int32_t vec;           /* 1: the 16-byte aligned input path */
+  int32_t groups;        /* split-K: chunk groups */
+  int32_t lean;          /* split-K: 1 = the lean finish kernel, 0 = the general one */
+  int32_t gemm;          /* ws4: 1 = GEMM mode, 0 = conv mode */
+  int32_t pre;           /* ws4: prologue kind (0 none, 1 LeakyReLU, 2 Snake, 3 SnakeBeta, 4 ELU) */
+  int32_t epi;           /* ws4: epilogue family (0 none / LeakyReLU, 1 GELU, 2 SiLU, 3 GELU-tanh) */
+  int32_t fq;            /* ws4: 1 = a quantising-prologue instantiation */
+  int32_t two_by_two;    /* ws4: 1 = the precision-5 build with the 2 x 2 consumer layout */
+  int32_t dbg;           /* ws4: 1 = the timeline-probe build */
+  int32_t abl;           /* ws4: timing-ablation build (0 = none) */
+  int32_t feat;          /* ws4: feature bits after the per-precision mask */
+  /* ws4: the geometry that does not depend on the device (the grid is sized at launch time from the CU count and mi355_conv_ws4_resident) */
+  int32_t tiles_per_item;
+  int32_t P;
+  int32_t NT;            /* row tiles per item, row tiles, column tiles */
+  int32_t nch;
+  int32_t keff;
+  int32_t tap_rows;      /* chunks per tile, taps per chunk, LDS row shift per tap */
+  int32_t R;             /* window rows */
+  int32_t nslices;       /* weight slices of the packed image */
+  int32_t fold;
+  int32_t glog;
+  int32_t total_ids;     /* residual folded into the accumulators, log2 of the XCD run length, virtual workgroup ids */
+} mi355_conv_route;
+/* Validates `a` and decides like mi355_conv_gemm, launches nothing and needs no device: *out = the route; a launch mi355_conv_gemm would refuse
+ * returns that call's error code and mi355_last_error text and leaves *out alone.  No pointer of `a` is dereferenced. */
+int mi355_conv_gemm_route(const mi355_conv_gemm_args* a, mi355_conv_route* out);
 /* 1 = this launch can write ext_partial (pre_fq set, precision 2, plain store, a prologue / epilogue pair the wave-specialised kernel's quantising
  * instantiations carry, 16-byte aligned channels-last rows); 0 otherwise.  ext_partial itself need not be set in the probe. */
 int mi355_conv_gemm_ext_supported(const mi355_conv_gemm_args* a);

@@ -394,9 +394,32 @@ __device__ __forceinline__ void conv_epilogue_up_interior(const mi355_conv_gemm_
 
 }  // namespace mi355conv
 
-// conv_ws4.hip: wave-specialised kernel (tile code 6128128 [+ 10000000 * feature bits for A/B runs]).  `feat` bit 0: consumers at default
-// priority (A/B aid; they run at s_setprio 1 otherwise), bit 2: timeline probe build, bit 3: one workgroup per tile instead of persistent
-// workgroups, bits 4..: timing ablations.  Returns MI355_ERR_UNSUPPORTED (and sets the error text) for argument combinations it has no
-// instantiation for.
-int mi355_conv_ws4_launch(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn = 128);
-bool mi355_conv_ws4_eligible(const mi355_conv_gemm_args& a, bool vec);
+// ---- host side: mi355_conv_gemm decides, then launches (conv_gemm.hip) ------------------------------------------------------------------------
+struct conv_route;
+typedef int (*conv_launch_fn)(const mi355_conv_gemm_args& a, hipStream_t st, const conv_route& r);
+// What the routing function decided for one launch: the public record and the launcher of the instantiation it names.
+struct conv_route : mi355_conv_route {
+  conv_launch_fn run;
+};
+
+// The A/B and bisecting knobs of the environment.  conv_knobs() (conv_gemm.hip) reads each once per process; none is set in production.
+struct conv_knob_set {
+  int split;            // 0 = the automatic choice never splits K
+  int split_minsteps;   // least (chunk, tap) steps per split-K group
+  bool finish_old;      // split-K always finishes with the general kernel
+  bool novec_flat;      // flattened strided convs (flat_valid > 0) keep off the 16-byte input path
+  int ws_feat;          // feature bits of the automatic choice's wave-specialised launches (below)
+  long ws_min_tiles;    // 128 x 128 tiles from which the automatic choice takes the wave-specialised kernel
+  bool no_ws, no_ws64;  // the automatic choice stays on the 4-wave kernels (no_ws64: for C_out <= 64 only)
+  int ws_wg_per_cu;     // persistent workgroups per CU of the wave-specialised kernel
+};
+const conv_knob_set& conv_knobs();
+
+// conv_ws4.hip: the wave-specialised kernel (tile codes 6128128 / 6128064 [+ 10000000 * feature bits for A/B runs]).  `feat` bit 0: consumers at
+// default priority (A/B aid; they run at s_setprio 1 otherwise), bit 1: masked producer body only (precision 5: the 2 x 2 consumer layout), bit 2:
+// timeline probe build, bit 3: one workgroup per tile instead of persistent workgroups, bits 4..: timing ablations.
+// mi355_conv_ws4_route fills `r` (launcher included) from the one instantiation list of precision `prec`'s file; MI355_ERR_UNSUPPORTED, with no
+// error text, when the list has no instantiation for the launch (mi355_conv_ws4_no_instantiation: the refusal for callers that cannot fall back).
+int mi355_conv_ws4_route(const mi355_conv_gemm_args& a, int prec, int feat, int bn, conv_route& r);
+int mi355_conv_ws4_no_instantiation(const mi355_conv_gemm_args& a, int prec, int bn);
+bool mi355_conv_ws4_eligible(const mi355_conv_gemm_args& a, int prec, bool vec);

@@ -248,18 +248,18 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const mi355_conv_ge
   conv_epilogue<MF, NF, WM, WN, SPLIT ? 0 : -1>(a, acc, SPLIT ? (int)blockIdx.z : b, l0, n0, wm, wn, lane, len_out, false);
 }
 
-// e4m3 tap-pair slices per chunk of the weight image of the call being dispatched (MX images handed to these kernels: they run the precision-4
-// arithmetic on the fp16 slices and skip the rest); set by mi355_conv_gemm for the duration of one call
-thread_local int t_mx_lo_slices = 0;
+// LDS bytes of a 4-wave / split-K launch: the activation window's 16-bit images and the double-buffered weight slice
+size_t conv_lds_bytes(const mi355_conv_gemm_args& a, const conv_route& r) {
+  const int R = r.bm + (a.K - 1) * a.dil;
+  return (size_t)R * 64 * ((r.precision == 2 || r.precision == 4) ? 2 : 1) + 2 * (r.bn / 32) * 2048;
+}
 
+// (r.mx_lo_slices: an MX image handed to these kernels -- they run the precision-4 arithmetic on its fp16 slices and skip the rest)
 template <int BM, int BN, int PREC, bool VEC>
-int launch(const mi355_conv_gemm_args& a, hipStream_t st) {
-  const int R = BM + (a.K - 1) * a.dil;
-  const size_t lds = (size_t)R * 64 * a_images<PREC>() + 2 * (BN / 32) * 2048;
-  MI355_REQUIRE(lds <= 64 * 1024, "conv_gemm: window too large for LDS (K=%d dil=%d)", a.K, a.dil);
+int launch(const mi355_conv_gemm_args& a, hipStream_t st, const conv_route& r) {
   dim3 grid((a.Lout + BM - 1) / BM, (a.Cout + BN - 1) / BN, a.B);
   MI355_CLEAR_ERROR();
-  hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, PREC, VEC>), grid, dim3(kThreads), lds, st, a, split_geom{1, 0, t_mx_lo_slices});
+  hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, PREC, VEC>), grid, dim3(kThreads), conv_lds_bytes(a, r), st, a, split_geom{1, 0, r.mx_lo_slices});
   MI355_LAUNCH_CHECK("conv_gemm");
   return MI355_OK;
 }
@@ -519,11 +519,11 @@ __global__ __launch_bounds__(256) void conv_split_finish_lean_kernel(const mi355
 // chunk groups for a launch of `wgs` tiles (0 = do not split): enough workgroups for two per CU, at least `min_steps` (chunk, tap) steps per group
 int split_groups(const long wgs, const int nchunks, const int K, const long rows_total, const int Cout, const int64_t ws_bytes, const int forced) {
   if (nchunks < 2) return 0;
-  static const int off = getenv("MI355_CONV_SPLIT") ? atoi(getenv("MI355_CONV_SPLIT")) : -1;   // 0 = never split (A/B aid)
-  if (off == 0 && !forced) return 0;
-  static const int min_steps = getenv("MI355_CONV_SPLIT_MINSTEPS") ? atoi(getenv("MI355_CONV_SPLIT_MINSTEPS")) : 4;   // A/B knob.  Round 4, calls 15 / 18: 2 is 0.27 ms faster on the 7.7 ms one-utterance pass (1 is not), but a different grouping between a
+  if (conv_knobs().split == 0 && !forced) return 0;
+  // (split_minsteps.  Round 4, calls 15 / 18: 2 is 0.27 ms faster on the 7.7 ms one-utterance pass (1 is not), but a different grouping between a
   // batch and a lone utterance moves F0 by 5e-6 relative, which is enough to wrap a harmonic phase feature (atan2 at +-pi) in the free-running
-  // batch-vs-single tests (tools/diag_batch_single.py): kept at 4 until those tests inject the source
+  // batch-vs-single tests (tools/diag_batch_single.py): kept at 4 until those tests inject the source)
+  const int min_steps = conv_knobs().split_minsteps;
   const int min_chunks = K >= min_steps ? 1 : (min_steps + K - 1) / K;       // >= min_steps (chunk, tap) steps per group
   int ks = forced;                                            // > 0: that many groups; -1: the rule's count whatever the tile count; 0: the rule
   if (ks <= 0) {
@@ -546,12 +546,9 @@ int split_groups(const long wgs, const int nchunks, const int K, const long rows
 }
 
 template <int BM, int BN, int PREC>
-int launch_split(const mi355_conv_gemm_args& a, hipStream_t st, const int ks) {
-  const int R = BM + (a.K - 1) * a.dil;
-  const size_t lds = (size_t)R * 64 * a_images<PREC>() + 2 * (BN / 32) * 2048;
-  MI355_REQUIRE(lds <= 64 * 1024, "conv_gemm: window too large for LDS (K=%d dil=%d)", a.K, a.dil);
-  const int nchunks = (a.Cin + 31) >> 5;
-  const split_geom sg{ks, (nchunks + ks - 1) / ks, t_mx_lo_slices};
+int launch_split(const mi355_conv_gemm_args& a, hipStream_t st, const conv_route& r) {
+  const int ks = r.groups, nchunks = (a.Cin + 31) >> 5;
+  const split_geom sg{ks, (nchunks + ks - 1) / ks, r.mx_lo_slices};
   const int ldp = (a.Cout + 3) & ~3;
   const int64_t slab = (int64_t)a.Lout * ldp;
   mi355_conv_gemm_args p = a;   // the partial pass: same input side, raw store into slab (b, kz)
@@ -562,33 +559,53 @@ int launch_split(const mi355_conv_gemm_args& a, hipStream_t st, const int ks) {
   p.res = nullptr; p.accumulate = 0; p.out_scale = 1.f;
   p.up_s = 0; p.lens_up = nullptr; p.stats_partial = nullptr;
   MI355_CLEAR_ERROR();
-  hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, PREC, true, true>), dim3((a.Lout + BM - 1) / BM, (a.Cout + BN - 1) / BN, a.B * ks), dim3(kThreads), lds, st, p, sg);
+  hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, PREC, true, true>), dim3((a.Lout + BM - 1) / BM, (a.Cout + BN - 1) / BN, a.B * ks), dim3(kThreads), conv_lds_bytes(a, r), st, p, sg);
   MI355_LAUNCH_CHECK("conv_gemm (split)");
-  static const bool lean_off = getenv("MI355_CONV_FINISH_OLD") != nullptr && getenv("MI355_CONV_FINISH_OLD")[0] == '1';   // A/B knob
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  const bool lean = !lean_off && !a.up_s && a.Cout % 4 == 0 && al16(a.bias) && al16(a.post_colscale) && al16(a.res) && al16(a.y) && al16(a.split_ws) &&
-                    a.ldy % 4 == 0 && a.y_bstride % 4 == 0 && (!a.res || (a.ldr % 4 == 0 && a.res_bstride % 4 == 0));
-  if (lean) hipLaunchKernelGGL(conv_split_finish_lean_kernel, dim3((a.Lout + 63) / 64, (a.Cout + 63) / 64, a.B), dim3(256), 0, st, a, (const float*)a.split_ws, ks, slab, ldp);
+  if (r.lean) hipLaunchKernelGGL(conv_split_finish_lean_kernel, dim3((a.Lout + 63) / 64, (a.Cout + 63) / 64, a.B), dim3(256), 0, st, a, (const float*)a.split_ws, ks, slab, ldp);
   else hipLaunchKernelGGL(conv_split_finish_kernel, dim3((a.Lout + 63) / 64, (a.Cout + 63) / 64, a.B), dim3(256), 0, st, a, (const float*)a.split_ws, ks, slab, ldp);
   MI355_LAUNCH_CHECK("conv_gemm (split finish)");
   return MI355_OK;
 }
 
-template <int BM, int BN>
-int launch_split_p(const mi355_conv_gemm_args& a, hipStream_t st, const int ks) {
-  switch (a.precision) {
-    case 1: return launch_split<BM, BN, 1>(a, st, ks);
-    case 3: return launch_split<BM, BN, 3>(a, st, ks);
-    case 4: return launch_split<BM, BN, 4>(a, st, ks);
-    default: return launch_split<BM, BN, 2>(a, st, ks);
+// ---------------------------------------------------------------------------------------------- the dispatcher: validate, decide, launch
+// Every instantiation of the 4-wave kernel, once: the launcher of a decided 4-wave / split-K route at precision PREC (nullptr: no such tile).
+template <int PREC>
+conv_launch_fn launcher_of(const conv_route& r) {
+  const int tile = r.bm * 1000 + r.bn;
+  if (r.family == MI355_ROUTE_SPLITK) return tile == 64128 ? launch_split<64, 128, PREC> : launch_split<64, 64, PREC>;
+  if (!r.vec) {
+    if constexpr (PREC != 1) return launch<64, 64, PREC, false>;
+    return nullptr;
+  }
+  switch (tile) {
+    case 128128: return launch<128, 128, PREC, true>;
+    case 64128: return launch<64, 128, PREC, true>;
+    case 64064: return launch<64, 64, PREC, true>;
+  }
+  return nullptr;
+}
+conv_launch_fn launcher_of(const conv_route& r) {   // the precision dispatch
+  switch (r.precision) {
+    case 1: return launcher_of<1>(r);
+    case 3: return launcher_of<3>(r);
+    case 4: return launcher_of<4>(r);
+    default: return launcher_of<2>(r);
   }
 }
 
-}  // namespace
+// The tile code, decoded once.  6128128 / 6128064: `digit` = feature bits, `abl` = ablation build; 2064128 / 2064064: `high` = groups (0 = the rule's count).
+struct tile_code {
+  int base;    // the code without its decimal digits from the ten-millions up
+  int high;    // those digits as a number
+  int digit;   // ... its ten-millions digit
+  int abl;     // ... its hundred-millions digits
+};
+tile_code decode_tile_code(const int tile) { return {tile % 10000000, tile / 10000000, (tile / 10000000) % 10, tile / 100000000}; }
 
-namespace {
+// 16-byte loads of four channels: aligned rows; a flattened strided conv (flat_valid > 0) qualifies when its run bounds are multiples of 4 too
 bool conv_vec_path(const mi355_conv_gemm_args& a) {
-  return (a.flat_valid % 4 == 0) && (a.ldx % 4 == 0) && (a.x_off % 4 == 0) && (a.x_bstride % 4 == 0) && (((uintptr_t)a.x) % 16 == 0);
+  return (a.flat_valid % 4 == 0) && (a.ldx % 4 == 0) && (a.x_off % 4 == 0) && (a.x_bstride % 4 == 0) && (((uintptr_t)a.x) % 16 == 0) &&
+         !(conv_knobs().novec_flat && a.flat_valid > 0);
 }
 // launches that can write per-block extrema: the quantising-prologue instantiations of the wave-specialised kernel (conv_ws4_fq.hip)
 bool conv_ext_supported(const mi355_conv_gemm_args& a) {
@@ -596,17 +613,13 @@ bool conv_ext_supported(const mi355_conv_gemm_args& a) {
   if (a.pre_act != MI355_ACT_NONE && a.pre_act != MI355_ACT_LEAKY && !(a.pre_act == MI355_ACT_SNAKE && !a.pre_inv_beta)) return false;
   if (a.post_act != MI355_ACT_NONE && a.post_act != MI355_ACT_LEAKY) return false;
   if (a.Cin < (a.Cout <= 64 ? 32 : 64)) return false;
-  mi355_conv_gemm_args t = a;
-  t.precision = 2;
-  return mi355_conv_ws4_eligible(t, conv_vec_path(a));
+  return mi355_conv_ws4_eligible(a, 2, conv_vec_path(a));
 }
-}  // namespace
 
-extern "C" int mi355_conv_gemm_ext_supported(const mi355_conv_gemm_args* ap) { return ap && conv_ext_supported(*ap) ? 1 : 0; }
-
-extern "C" int mi355_conv_gemm(const mi355_conv_gemm_args* ap, void* stream) {
+// Step 1: the argument checks, into a copy with the defaults filled in (precision 0 -> 2, out_scale 0 -> 1, no split-K workspace under y_split).
+int conv_validate(const mi355_conv_gemm_args* ap, mi355_conv_gemm_args& a) {
   MI355_REQUIRE(ap, "conv_gemm: null args");
-  mi355_conv_gemm_args a = *ap;
+  a = *ap;
   MI355_REQUIRE(a.x && a.w && a.y, "conv_gemm: null tensor");
   MI355_REQUIRE(a.B > 0 && a.Lout > 0 && a.Cout > 0 && a.Cin > 0 && a.K > 0, "conv_gemm: bad shape");
   MI355_REQUIRE(a.dil >= 1, "conv_gemm: dilation must be >= 1");
@@ -623,136 +636,166 @@ extern "C" int mi355_conv_gemm(const mi355_conv_gemm_args* ap, void* stream) {
   MI355_REQUIRE(!a.pre_fq || a.pre_act == MI355_ACT_NONE || a.pre_act == MI355_ACT_LEAKY || (a.pre_act == MI355_ACT_SNAKE && !a.pre_inv_beta),
                 "conv_gemm: a quantising prologue (pre_fq) takes no activation, LeakyReLU or Snake");
   if (a.out_scale == 0.f) a.out_scale = 1.f;
-  hipStream_t st = (hipStream_t)stream;
-  // 16-byte loads of four channels: aligned rows; a flattened strided conv (flat_valid > 0) qualifies when its run bounds are multiples of 4 too
-  static const bool novec_flat = getenv("MI355_CONV_NOVEC_FLAT") != nullptr && getenv("MI355_CONV_NOVEC_FLAT")[0] == '1';   // A/B knob
-  const bool vec = (a.flat_valid % 4 == 0) && (a.ldx % 4 == 0) && (a.x_off % 4 == 0) && (a.x_bstride % 4 == 0) &&
-                   (((uintptr_t)a.x) % 16 == 0) && !(novec_flat && a.flat_valid > 0);
   if (a.stats_partial) {
     MI355_REQUIRE(a.up_s == 0, "conv_gemm: fused statistics need a plain (non-polyphase) store");
     MI355_REQUIRE(a.stats_bstride % 2 == 0 && ((uintptr_t)a.stats_partial) % 8 == 0, "conv_gemm: stats_partial must be 8-byte aligned");
   }
-  int tile = a.tile;
-  t_mx_lo_slices = 0;
   if (a.y_split) {
     MI355_REQUIRE(a.y_split == 2 || a.y_split == 4, "conv_gemm: y_split must be 0, 2 (bfloat16 hi | lo) or 4 (IEEE half hi | lo)");
     MI355_REQUIRE(!a.accumulate, "conv_gemm: y_split cannot accumulate into y (y holds split words)");
     a.split_ws = nullptr;   // (the split-K finish kernel stores floats)
   }
-  if (a.x_split) {   // pre-split activations: the wave-specialised kernel's producers only (whatever the tile count)
+  if (a.x_split) {
     MI355_REQUIRE(a.x_split == a.precision && (a.precision == 2 || a.precision == 4), "conv_gemm: x_split must equal the launch's precision, 2 or 4");
     MI355_REQUIRE(a.pre_act == MI355_ACT_NONE && !a.pre_scale && !a.pre_fq, "conv_gemm: a split input takes no prologue");
-    MI355_REQUIRE(!a.ext_partial && mi355_conv_ws4_eligible(a, vec), "conv_gemm: x_split needs 16-byte aligned channels-last rows and a window of <= 192 rows "
+  }
+  return MI355_OK;
+}
+
+// Step 2: which kernel runs a validated launch.  Pure host code: no HIP call, no pointer of `a` followed (null-ness and alignment only), nothing
+// written but `r` and, for a launch no kernel takes, the error text.
+int conv_decide(const mi355_conv_gemm_args& a, conv_route& r) {
+  const conv_knob_set& env = conv_knobs();
+  const tile_code t = decode_tile_code(a.tile);
+  const bool vec = conv_vec_path(a);
+  r = conv_route{};
+  r.precision = a.precision;
+  r.vec = vec;
+  auto ws4 = [&](const int feat, const int bn) { return mi355_conv_ws4_route(a, r.precision, feat, bn, r); };
+  auto ws4_or_refuse = [&](const int feat, const int bn) {   // callers with no kernel to fall back to
+    const int rc = ws4(feat, bn);
+    return rc == MI355_ERR_UNSUPPORTED ? mi355_conv_ws4_no_instantiation(a, r.precision, bn) : rc;
+  };
+  auto split = [&](const bool wide, const int ks) -> int {
+    r.family = MI355_ROUTE_SPLITK; r.bm = 64; r.bn = wide ? 128 : 64; r.groups = ks;
+    auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+    r.lean = !env.finish_old && !a.up_s && a.Cout % 4 == 0 && al16(a.bias) && al16(a.post_colscale) && al16(a.res) && al16(a.y) && al16(a.split_ws) &&
+             a.ldy % 4 == 0 && a.y_bstride % 4 == 0 && (!a.res || (a.ldr % 4 == 0 && a.res_bstride % 4 == 0));
+    r.run = launcher_of(r);
+    MI355_REQUIRE(conv_lds_bytes(a, r) <= 64 * 1024, "conv_gemm: window too large for LDS (K=%d dil=%d)", a.K, a.dil);
+    return MI355_OK;
+  };
+  if (a.x_split) {   // pre-split activations: the wave-specialised kernel's producers only (whatever the tile count)
+    MI355_REQUIRE(!a.ext_partial && mi355_conv_ws4_eligible(a, a.precision, vec), "conv_gemm: x_split needs 16-byte aligned channels-last rows and a window of <= 192 rows "
                   "(the wave-specialised kernel)");
-    static const int ws_feat_x = getenv("MI355_CONV_WS_FEAT") ? atoi(getenv("MI355_CONV_WS_FEAT")) : 0;
-    const int rc = a.Cout <= 64 ? mi355_conv_ws4_launch(a, st, ws_feat_x & 3, 64) : mi355_conv_ws4_launch(a, st, tile % 10000000 == 6128128 ? ((tile / 10000000) % 10) : ws_feat_x);
-    return rc;
+    return a.Cout <= 64 ? ws4_or_refuse(env.ws_feat & 3, 64) : ws4_or_refuse(t.base == 6128128 ? t.digit : env.ws_feat, 128);
   }
   if (a.ext_partial) {   // per-block extrema: only the quantising instantiations of the wave-specialised kernel write them -- no other path may take the launch
     MI355_REQUIRE(conv_ext_supported(a), "conv_gemm: ext_partial needs a launch mi355_conv_gemm_ext_supported accepts (pre_fq, precision 2, plain store, K > 1)");
     MI355_REQUIRE(a.ext_bstride % 2 == 0 && ((uintptr_t)a.ext_partial) % 8 == 0, "conv_gemm: ext_partial must be 8-byte aligned");
-    static const int ws_feat_e = getenv("MI355_CONV_WS_FEAT") ? atoi(getenv("MI355_CONV_WS_FEAT")) : 0;
-    return mi355_conv_ws4_launch(a, st, ws_feat_e & 3, a.Cout <= 64 ? 64 : 128);
+    return ws4_or_refuse(env.ws_feat & 3, a.Cout <= 64 ? 64 : 128);
   }
   if (a.precision == 5 || a.precision == 6) {
     // the wave-specialised kernel takes the launch when it fills the chip (the same rule as the auto choice below) or when asked for by tile
     // code; everything else runs the precision-4 arithmetic of the 4-wave kernels on the image's fp16 slices
-    static const long ws_min5 = getenv("MI355_CONV_WS_MIN_TILES") ? atol(getenv("MI355_CONV_WS_MIN_TILES")) : 128;
-    static const bool no_ws5 = getenv("MI355_CONV_NO_WS") != nullptr;
     const long wgs128 = (long)a.B * ((a.Lout + 127) / 128) * ((a.Cout + 127) / 128);
-    const bool want = tile % 10000000 == 6128128 || (tile == 0 && !no_ws5 && a.Cout > 64 && wgs128 >= ws_min5 && a.Cin >= 64);
-    if (want && mi355_conv_ws4_eligible(a, vec)) {
-      const int rc = mi355_conv_ws4_launch(a, st, tile == 0 ? 0 : (((tile / 10000000) % 10) | ((tile / 100000000) << 4)));   // feature / probe / ablation bits
+    const bool want = t.base == 6128128 || (a.tile == 0 && !env.no_ws && a.Cout > 64 && wgs128 >= env.ws_min_tiles && a.Cin >= 64);
+    if (want && mi355_conv_ws4_eligible(a, a.precision, vec)) {
+      const int rc = ws4(a.tile == 0 ? 0 : (t.digit | (t.abl << 4)), 128);   // feature / probe / ablation bits
       if (rc != MI355_ERR_UNSUPPORTED) return rc;
     }
-    MI355_REQUIRE(tile % 10000000 != 6128128, "conv_gemm: precisions 5 / 6 on the wave-specialised tile needs K = 3 (mod 4), a plain / LeakyReLU / Snake prologue, "
+    MI355_REQUIRE(t.base != 6128128, "conv_gemm: precisions 5 / 6 on the wave-specialised tile needs K = 3 (mod 4), a plain / LeakyReLU / Snake prologue, "
                   "no epilogue activation beyond LeakyReLU and 16-B aligned channels-last rows");
-    t_mx_lo_slices = (a.K + 1) >> 1;
-    a.precision = 4;   // (the precision-4 instantiations of the wave-specialised kernel do not know the MX slice layout: mx_image below)
+    r.mx_fallback = 1;   // (the precision-4 instantiations of the wave-specialised kernel do not know the MX slice layout: no ws4 below)
+    r.mx_lo_slices = (a.K + 1) >> 1;
+    r.precision = 4;
   }
-  const bool mx_image = t_mx_lo_slices != 0;
-  if (tile == 0) {
+  int four = a.tile;   // the 4-wave tile, BM * 1000 + BN, unless a branch below returns
+  if (a.tile == 0) {
     const int bn = a.Cout <= 64 ? 64 : 128;
     const long wgs128 = (long)a.B * ((a.Lout + 127) / 128) * ((a.Cout + bn - 1) / bn);
-    const int bm = (bn == 128 && wgs128 >= 512) ? 128 : 64;
-    tile = bm * 1000 + bn;
     // the wave-specialised kernel once there are enough 128 x 128 tiles to occupy the 256 CUs
-    // (MI355_CONV_NO_WS=1 in the environment keeps the auto choice on the 4-wave kernels: an A/B and bisecting aid;
-    // MI355_CONV_WS_FEAT = feature bits of conv_common.h; MI355_CONV_WS_MIN_TILES overrides the fill threshold)
-    static const bool no_ws = getenv("MI355_CONV_NO_WS") != nullptr;
-    static const int ws_feat = getenv("MI355_CONV_WS_FEAT") ? atoi(getenv("MI355_CONV_WS_FEAT")) : 0;
-    static const long ws_min = getenv("MI355_CONV_WS_MIN_TILES") ? atol(getenv("MI355_CONV_WS_MIN_TILES")) : 128;
     // (shallow inputs, C_in < 64: a tile is one chunk of work and an epilogue -- store bound.  From 2048 tiles on the persistent kernel's interior epilogue wins
     // 2.2x over the 4-wave kernels: Kokoro's 22 -> 128 source conv at 2 M rows 0.60 -> 0.26 ms, profiles/r6_conv_thin_b64_call19.txt)
-    if (!no_ws && !mx_image && bn == 128 && wgs128 >= ws_min && (a.Cin >= 64 || wgs128 >= 2048) && mi355_conv_ws4_eligible(a, vec)) {
-      const int rc = mi355_conv_ws4_launch(a, st, ws_feat);
-      if (rc != MI355_ERR_UNSUPPORTED) return rc;  // no instantiation for this prologue / epilogue pair: fall through to the 4-wave kernels
+    // thin outputs (C_out <= 64): the same kernel on 128 x 64 tiles
+    const bool fills = !env.no_ws && !r.mx_fallback && wgs128 >= env.ws_min_tiles;
+    const bool deep = bn == 128 ? a.Cin >= 64 || wgs128 >= 2048 : !env.no_ws64 && a.Cin >= 32;
+    if (fills && deep && mi355_conv_ws4_eligible(a, r.precision, vec)) {
+      const int rc = ws4(bn == 128 ? env.ws_feat : env.ws_feat & 3, bn);
+      if (rc != MI355_ERR_UNSUPPORTED) return rc;  // no instantiation for this prologue / epilogue pair: the 4-wave kernels below
     }
-    // thin outputs (C_out <= 64): the same kernel on 128 x 64 tiles (MI355_CONV_NO_WS64=1 keeps them on the 4-wave 64 x 64 kernel: A/B aid)
-    static const bool no_ws64 = getenv("MI355_CONV_NO_WS64") != nullptr;
-    if (!no_ws && !no_ws64 && !mx_image && bn == 64 && wgs128 >= ws_min && a.Cin >= 32 && mi355_conv_ws4_eligible(a, vec)) {
-      const int rc = mi355_conv_ws4_launch(a, st, ws_feat & 3, 64);
-      if (rc != MI355_ERR_UNSUPPORTED) return rc;
-    }
-    if (bn == 128 && wgs128 >= 512) tile = 64128;  // measured: 64-row tiles beat 128-row tiles on the 4-wave kernel
+    four = 64000 + bn;  // measured: 64-row tiles beat 128-row tiles on the 4-wave kernel, at 512 tiles and more too
     if (a.split_ws && vec) {   // few tiles and a deep K loop: cut the chunk range over several workgroups per tile (64-row tiles)
       const long wgs64 = (long)a.B * ((a.Lout + 63) / 64) * ((a.Cout + bn - 1) / bn);
       const int ks = split_groups(wgs64, (a.Cin + 31) >> 5, a.K, (long)a.B * a.Lout, a.Cout, a.split_ws_bytes, 0);
-      if (ks) return bn == 128 ? launch_split_p<64, 128>(a, st, ks) : launch_split_p<64, 64>(a, st, ks);
+      if (ks) return split(bn == 128, ks);
     }
   }
-  if (tile % 10000000 == 2064128 || tile % 10000000 == 2064064) {  // split-K, explicit: + 10000000 * groups (0 = as many as the rule gives)
+  if (t.base == 2064128 || t.base == 2064064) {  // split-K, explicit: + 10000000 * groups (0 = as many as the rule gives)
     MI355_REQUIRE(vec && a.split_ws, "conv_gemm: the split-K tiles need the 16-B aligned channels-last input path and a workspace (split_ws)");
-    const bool wide = tile % 10000000 == 2064128;
+    const bool wide = t.base == 2064128;
     const long wgs64 = (long)a.B * ((a.Lout + 63) / 64) * ((a.Cout + (wide ? 127 : 63)) / (wide ? 128 : 64));
-    const int ks = split_groups(wgs64, (a.Cin + 31) >> 5, a.K, (long)a.B * a.Lout, a.Cout, a.split_ws_bytes, tile / 10000000 ? tile / 10000000 : -1);
+    const int ks = split_groups(wgs64, (a.Cin + 31) >> 5, a.K, (long)a.B * a.Lout, a.Cout, a.split_ws_bytes, t.high ? t.high : -1);
     MI355_REQUIRE(ks >= 2, "conv_gemm: nothing to split (C_in %d, K %d, workspace %lld bytes)", a.Cin, a.K, (long long)a.split_ws_bytes);
-    return wide ? launch_split_p<64, 128>(a, st, ks) : launch_split_p<64, 64>(a, st, ks);
+    return split(wide, ks);
   }
-  if (tile % 10000000 == 6128064) {  // ws4 on 128 x 64 tiles, explicit (+ 10000000 * feature bits 0..3)
-    MI355_REQUIRE(!mx_image, "conv_gemm: MX images (precision 5) have no 128 x 64 wave-specialised tile");
-    MI355_REQUIRE(mi355_conv_ws4_eligible(a, vec), "conv_gemm: the wave-specialised tile needs 16-B aligned channels-last input rows and a window of <= 192 rows");
-    return mi355_conv_ws4_launch(a, st, (tile / 10000000) & 11, 64);
+  if (t.base == 6128064) {  // ws4 on 128 x 64 tiles, explicit (+ 10000000 * feature bits 0..3)
+    MI355_REQUIRE(!r.mx_fallback, "conv_gemm: MX images (precision 5) have no 128 x 64 wave-specialised tile");
+    MI355_REQUIRE(mi355_conv_ws4_eligible(a, r.precision, vec), "conv_gemm: the wave-specialised tile needs 16-B aligned channels-last input rows and a window of <= 192 rows");
+    return ws4_or_refuse(t.high & 11, 64);
   }
-  if (tile % 10000000 == 6128128) {  // ws4, explicit: 6128128 + 10000000 * feature bits (+ 100000000 * ablation bits)
-    MI355_REQUIRE(mi355_conv_ws4_eligible(a, vec), "conv_gemm: the wave-specialised tile needs 16-B aligned channels-last input rows and a window of <= 192 rows");
-    return mi355_conv_ws4_launch(a, st, ((tile / 10000000) % 10) | ((tile / 100000000) << 4));
+  if (t.base == 6128128) {  // ws4, explicit: 6128128 + 10000000 * feature bits (+ 100000000 * ablation bits)
+    MI355_REQUIRE(mi355_conv_ws4_eligible(a, r.precision, vec), "conv_gemm: the wave-specialised tile needs 16-B aligned channels-last input rows and a window of <= 192 rows");
+    return ws4_or_refuse(t.digit | (t.abl << 4), 128);
   }
   if (a.stats_partial) {  // statistics are produced per 64-row wave block: only the 128-row kernels have those
     MI355_REQUIRE(vec, "conv_gemm: fused statistics need the 16-B aligned channels-last input path");
-    tile = 128128;
+    four = 128128;
   }
   if (!vec) {
-    if (a.precision == 3) return launch<64, 64, 3, false>(a, st);
-    if (a.precision == 4) return launch<64, 64, 4, false>(a, st);
-    a.precision = 2;  // with bf16 weights the unaligned (tiny C_in) path always runs the hi+lo split
-    return launch<64, 64, 2, false>(a, st);
+    four = 64064;
+    if (r.precision == 1) r.precision = 2;  // with bf16 weights the unaligned (tiny C_in) path always runs the hi+lo split
   }
-  if (a.precision == 2) {
-    switch (tile) {
-      case 128128: return launch<128, 128, 2, true>(a, st);
-      case 64128: return launch<64, 128, 2, true>(a, st);
-      case 64064: return launch<64, 64, 2, true>(a, st);
-    }
-  } else if (a.precision == 3) {
-    switch (tile) {
-      case 128128: return launch<128, 128, 3, true>(a, st);
-      case 64128: return launch<64, 128, 3, true>(a, st);
-      case 64064: return launch<64, 64, 3, true>(a, st);
-    }
-  } else if (a.precision == 4) {
-    switch (tile) {
-      case 128128: return launch<128, 128, 4, true>(a, st);
-      case 64128: return launch<64, 128, 4, true>(a, st);
-      case 64064: return launch<64, 64, 4, true>(a, st);
-    }
-  } else {
-    switch (tile) {
-      case 128128: return launch<128, 128, 1, true>(a, st);
-      case 64128: return launch<64, 128, 1, true>(a, st);
-      case 64064: return launch<64, 64, 1, true>(a, st);
-    }
+  r.family = MI355_ROUTE_4WAVE; r.bm = four / 1000; r.bn = four % 1000;
+  r.run = launcher_of(r);
+  if (!r.run) {
+    mi355_set_error("conv_gemm: unsupported tile %d", four);
+    return MI355_ERR_UNSUPPORTED;
   }
-  mi355_set_error("conv_gemm: unsupported tile %d", tile);
-  return MI355_ERR_UNSUPPORTED;
+  MI355_REQUIRE(conv_lds_bytes(a, r) <= 64 * 1024, "conv_gemm: window too large for LDS (K=%d dil=%d)", a.K, a.dil);
+  return MI355_OK;
+}
+
+}  // namespace
+
+// the knobs: names, defaults and meanings (struct conv_knob_set, conv_common.h)
+const conv_knob_set& conv_knobs() {
+  static const conv_knob_set k = [] {
+    auto num = [](const char* name, const long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; };
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    auto one = [](const char* name) { const char* v = getenv(name); return v != nullptr && v[0] == '1'; };
+    conv_knob_set k;
+    k.split = (int)num("MI355_CONV_SPLIT", -1);
+    k.split_minsteps = (int)num("MI355_CONV_SPLIT_MINSTEPS", 4);
+    k.finish_old = one("MI355_CONV_FINISH_OLD");
+    k.novec_flat = one("MI355_CONV_NOVEC_FLAT");
+    k.ws_feat = (int)num("MI355_CONV_WS_FEAT", 0);
+    k.ws_min_tiles = num("MI355_CONV_WS_MIN_TILES", 128);
+    k.no_ws = set("MI355_CONV_NO_WS");
+    k.no_ws64 = set("MI355_CONV_NO_WS64");
+    k.ws_wg_per_cu = (int)num("MI355_CONV_WS_WG_PER_CU", 2);
+    return k;
+  }();
+  return k;
+}
+
+extern "C" int mi355_conv_gemm_ext_supported(const mi355_conv_gemm_args* ap) { return ap && conv_ext_supported(*ap) ? 1 : 0; }
+
+extern "C" int mi355_conv_gemm_route(const mi355_conv_gemm_args* ap, mi355_conv_route* out) {
+  MI355_REQUIRE(out, "conv_gemm_route: null record");
+  mi355_conv_gemm_args a;
+  conv_route r;
+  if (const int rc = conv_validate(ap, a)) return rc;
+  if (const int rc = conv_decide(a, r)) return rc;
+  *out = r;
+  return MI355_OK;
+}
+
+extern "C" int mi355_conv_gemm(const mi355_conv_gemm_args* ap, void* stream) {
+  mi355_conv_gemm_args a;
+  conv_route r;
+  if (const int rc = conv_validate(ap, a)) return rc;
+  if (const int rc = conv_decide(a, r)) return rc;
+  a.precision = r.precision;   // (an MX image on the precision-4 arithmetic, bf16 weights on the unaligned path)
+  return r.run(a, (hipStream_t)stream, r);   // step 3
 }

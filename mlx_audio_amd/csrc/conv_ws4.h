@@ -28,7 +28,10 @@
 
 namespace mi355conv {
 
-extern int g_ws4_resident;   // conv_ws4.hip; 0 = two workgroups per CU
+// conv_ws4.hip, read at launch time: the grid of a launch of `total_ids` virtual ids (persistent workgroups: a share of the chip set by
+// mi355_conv_ws4_resident, else a number per CU; feature bit 3: one workgroup per id) and the timeline probe's buffer
+unsigned ws4_grid(int total_ids, int feat);
+unsigned long long* ws4_debug_buffer();
 
 constexpr int kWs4Threads = 512;
 
@@ -1110,51 +1113,61 @@ __global__ __launch_bounds__(kWs4Threads, 4) void conv_ws4_kernel(const mi355_co
 // GEMM mode: pure linear layers (K == 1, no prologue) with at least two 32-channel chunks
 inline bool gemm_mode(const mi355_conv_gemm_args& a) { return a.K == 1 && a.Cin >= 64 && a.pre_act == MI355_ACT_NONE && !a.pre_scale && !a.pre_fq; }
 
-template <int PREC, int PRE, int EPI, bool GEMM, bool DBG = false, int ABL = 0, int BN = 128, bool FQ = false, bool CW = true>
-int launch_ws4(const mi355_conv_gemm_args& a, hipStream_t st, const int feat, unsigned long long* dbg = nullptr) {
+// One launch as the instantiation lists see it (mi355_conv_ws4_route, conv_ws4.hip): what selects an instantiation, and the route to fill.
+struct ws4_call {
+  const mi355_conv_gemm_args& a;
+  int prec;       // the launch's precision
+  int pre, epi;   // pre_kind, epi_family
+  bool gemm;      // gemm_mode (never at precisions 5 / 6: K == 1 layers run those kernels in conv mode, one hi item + one half-empty lo item per chunk)
+  int bn;
+  conv_route& r;
+};
+
+// the launch step of a route that route_ws4 filled
+template <int PREC, int PRE, int EPI, bool GEMM, bool DBG, int ABL, int BN, bool FQ, bool CW>
+int run_ws4(const mi355_conv_gemm_args& a, hipStream_t st, const conv_route& r) {
   ws4_geom q;
-  q.bn = BN;
-  q.gemm = GEMM ? 1 : 0;
-  const int chunks32 = (a.Cin + 31) >> 5;
-  q.nslices = chunks32 * ((PREC == 5 || PREC == 6) ? a.K + ((a.K + 1) >> 1) : a.K);
-  if (q.gemm) {
-    q.nch = (chunks32 + 1) >> 1;
-    q.keff = 2;
-    q.tap_rows = 128;
-    q.R = 256;
-  } else {
-    q.nch = chunks32;
-    q.keff = a.K;
-    q.tap_rows = a.dil;
-    q.R = 128 + (a.K - 1) * a.dil;
-  }
-  MI355_REQUIRE(q.R <= (GEMM ? 256 : 192), "conv_gemm(ws4): window of %d rows exceeds %d (K=%d dil=%d)", q.R, GEMM ? 256 : 192, a.K, a.dil);
+  q.tiles_per_item = r.tiles_per_item; q.P = r.P; q.NT = r.NT; q.glog = r.glog; q.fold = r.fold;
+  q.nch = r.nch; q.keff = r.keff; q.tap_rows = r.tap_rows; q.R = r.R; q.gemm = r.gemm; q.nslices = r.nslices;
+  q.bn = BN; q.feat = r.feat; q.total_ids = r.total_ids;
+  q.dbg = DBG ? ws4_debug_buffer() : nullptr;
   const size_t lds = (size_t)2 * window_bytes<PREC>(q.R);
-  q.tiles_per_item = (a.Lout + 127) / 128;
-  q.P = a.B * q.tiles_per_item;
-  q.NT = (a.Cout + BN - 1) / BN;
-  q.fold = ((a.res || a.accumulate) && a.post_act == MI355_ACT_NONE && a.up_s == 0 && a.res_shift == 0 && !a.post_colscale) ? 1 : 0;
-  // runs of 2^glog consecutive row tiles per XCD: long runs share halos in L2, but every XCD must still get several rounds of runs
-  q.glog = q.P >= 512 ? 3 : (q.P >= 256 ? 2 : (q.P >= 128 ? 1 : 0));
-  q.feat = feat;
-  q.dbg = dbg;
-  const int per = 8 << q.glog;
-  q.total_ids = ((q.P + per - 1) / per) * per * q.NT;
-  // persistent: two resident workgroups per CU (128 VGPRs x 8 waves each) walk the tile list; small problems launch one workgroup per tile
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  static const int wg_per_cu = getenv("MI355_CONV_WS_WG_PER_CU") ? atoi(getenv("MI355_CONV_WS_WG_PER_CU")) : 2;
-  // mi355_conv_ws4_resident(n): the next launches take at most n persistent workgroups (a share of the chip: several convs on separate streams)
-  const int resident = g_ws4_resident > 0 ? ((g_ws4_resident + 7) / 8) * 8 : ((cus * wg_per_cu) / 8) * 8;
-  const unsigned grid = (unsigned)((feat & 8) || q.total_ids <= resident ? q.total_ids : resident);  // feat bit 3: one workgroup per tile (A/B aid)
   MI355_CLEAR_ERROR();
-  hipLaunchKernelGGL((conv_ws4_kernel<PREC, PRE, EPI, GEMM, DBG, ABL, BN, FQ, CW>), dim3(grid), dim3(kWs4Threads), lds, st, a, q);
+  hipLaunchKernelGGL((conv_ws4_kernel<PREC, PRE, EPI, GEMM, DBG, ABL, BN, FQ, CW>), dim3(ws4_grid(r.total_ids, r.feat)), dim3(kWs4Threads), lds, st, a, q);
   MI355_LAUNCH_CHECK("conv_gemm(ws4)");
+  return MI355_OK;
+}
+
+// One instantiation, named by a line of a list: writes its template parameters, the launch's geometry and its launcher into the route.
+template <int PREC, int PRE, int EPI, bool GEMM, bool DBG = false, int ABL = 0, int BN = 128, bool FQ = false, bool CW = true>
+int route_ws4(const ws4_call& c, const int feat) {
+  const mi355_conv_gemm_args& a = c.a;
+  conv_route& r = c.r;
+  const int chunks32 = (a.Cin + 31) >> 5;
+  r.nslices = chunks32 * ((PREC == 5 || PREC == 6) ? a.K + ((a.K + 1) >> 1) : a.K);
+  if (GEMM) {
+    r.nch = (chunks32 + 1) >> 1;
+    r.keff = 2;
+    r.tap_rows = 128;
+    r.R = 256;
+  } else {
+    r.nch = chunks32;
+    r.keff = a.K;
+    r.tap_rows = a.dil;
+    r.R = 128 + (a.K - 1) * a.dil;
+  }
+  MI355_REQUIRE(r.R <= (GEMM ? 256 : 192), "conv_gemm(ws4): window of %d rows exceeds %d (K=%d dil=%d)", r.R, GEMM ? 256 : 192, a.K, a.dil);
+  r.tiles_per_item = (a.Lout + 127) / 128;
+  r.P = a.B * r.tiles_per_item;
+  r.NT = (a.Cout + BN - 1) / BN;
+  r.fold = ((a.res || a.accumulate) && a.post_act == MI355_ACT_NONE && a.up_s == 0 && a.res_shift == 0 && !a.post_colscale) ? 1 : 0;
+  // runs of 2^glog consecutive row tiles per XCD: long runs share halos in L2, but every XCD must still get several rounds of runs
+  r.glog = r.P >= 512 ? 3 : (r.P >= 256 ? 2 : (r.P >= 128 ? 1 : 0));
+  const int per = 8 << r.glog;
+  r.total_ids = ((r.P + per - 1) / per) * per * r.NT;
+  r.family = MI355_ROUTE_WS4; r.precision = PREC; r.bm = 128; r.bn = BN; r.vec = 1;
+  r.gemm = GEMM; r.pre = PRE; r.epi = EPI; r.fq = FQ; r.two_by_two = !CW; r.dbg = DBG; r.abl = ABL; r.feat = feat;
+  r.run = run_ws4<PREC, PRE, EPI, GEMM, DBG, ABL, BN, FQ, CW>;
   return MI355_OK;
 }
 
@@ -1181,23 +1194,24 @@ inline int pre_kind(const mi355_conv_gemm_args& a) {
   return -1;
 }
 
+// the lines of the instantiation lists (conv_ws4*.hip), inside a function of (const ws4_call& c, int feat)
 #define WS4_CASE(PREC, PRE, EPI) \
-  if (bn == 128 && pre == PRE && epi == EPI && !gemm) return launch_ws4<PREC, PRE, EPI, false>(a, st, feat)
+  if (c.bn == 128 && c.pre == PRE && c.epi == EPI && !c.gemm) return route_ws4<PREC, PRE, EPI, false>(c, feat)
 #define WS4_GEMM(PREC, EPI) \
-  if (bn == 128 && epi == EPI && gemm) return launch_ws4<PREC, P_NONE, EPI, true>(a, st, feat)
+  if (c.bn == 128 && c.epi == EPI && c.gemm) return route_ws4<PREC, P_NONE, EPI, true>(c, feat)
 // the 64-column tile (bn == 64: asked for by the dispatcher when the last 128-column tile would be at most half full)
 #define WS4_CASE_N64(PREC, PRE, EPI) \
-  if (bn == 64 && pre == PRE && epi == EPI && !gemm) return launch_ws4<PREC, PRE, EPI, false, false, 0, 64>(a, st, feat & 15)
+  if (c.bn == 64 && c.pre == PRE && c.epi == EPI && !c.gemm) return route_ws4<PREC, PRE, EPI, false, false, 0, 64>(c, feat & 15)
 #define WS4_GEMM_N64(PREC, EPI) \
-  if (bn == 64 && epi == EPI && gemm) return launch_ws4<PREC, P_NONE, EPI, true, false, 0, 64>(a, st, feat & 15)
+  if (c.bn == 64 && c.epi == EPI && c.gemm) return route_ws4<PREC, P_NONE, EPI, true, false, 0, 64>(c, feat & 15)
 
 }  // namespace mi355conv
 
-// per-precision instantiation sets (one translation unit each: they compile in parallel); MI355_ERR_UNSUPPORTED = no such instantiation
-int mi355_conv_ws4_p2(const mi355_conv_gemm_args& a, hipStream_t st, int feat, unsigned long long* dbg, int bn);
-int mi355_conv_ws4_p4(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn);
-int mi355_conv_ws4_p13(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn);
-int mi355_conv_ws4_fq(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn);   // quantising prologues (pre_fq), precision 2
-int mi355_conv_ws4_p5(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn);   // fp16 hi + MX e4m3 lo (conv mode, 128-column tiles)
-int mi355_conv_ws4_p6(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn);   // fp16 hi + MX FP4 lo (conv mode, 128-column tiles)
-int mi355_conv_ws4_p5_probe(const mi355_conv_gemm_args& a, hipStream_t st, int feat, unsigned long long* dbg);   // its probe / ablation builds
+// per-precision instantiation lists (one translation unit each: they compile in parallel); MI355_ERR_UNSUPPORTED = no such instantiation
+int mi355_conv_ws4_p2(const mi355conv::ws4_call& c, int feat);
+int mi355_conv_ws4_p4(const mi355conv::ws4_call& c, int feat);
+int mi355_conv_ws4_p13(const mi355conv::ws4_call& c, int feat);
+int mi355_conv_ws4_fq(const mi355conv::ws4_call& c, int feat);   // quantising prologues (pre_fq), precision 2
+int mi355_conv_ws4_p5(const mi355conv::ws4_call& c, int feat);   // fp16 hi + MX e4m3 lo (conv mode, 128-column tiles)
+int mi355_conv_ws4_p6(const mi355conv::ws4_call& c, int feat);   // fp16 hi + MX FP4 lo (conv mode, 128-column tiles)
+int mi355_conv_ws4_p5_probe(const mi355conv::ws4_call& c, int feat);   // the probe / ablation builds of precisions 5 and 6

@@ -5,28 +5,43 @@
 using namespace mi355conv;
 
 namespace {
-unsigned long long* g_dbg_buffer = nullptr;  // host copy of the probe buffer pointer (handed to the DBG instantiation through its geometry record)
+unsigned long long* g_dbg_buffer = nullptr;  // host copy of the probe buffer pointer (handed to the DBG instantiations through their geometry record)
+int g_ws4_resident = 0;                      // mi355_conv_ws4_resident; 0 = a number per CU
 }
 
 namespace mi355conv {
-int g_ws4_resident = 0;
+unsigned long long* ws4_debug_buffer() { return g_dbg_buffer; }
+
+// persistent: two resident workgroups per CU (128 VGPRs x 8 waves each) walk the tile list; small problems launch one workgroup per tile
+unsigned ws4_grid(const int total_ids, const int feat) {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+    if (cus <= 0) cus = 256;
+  }
+  // mi355_conv_ws4_resident(n): the next launches take at most n persistent workgroups (a share of the chip: several convs on separate streams)
+  const int resident = g_ws4_resident > 0 ? ((g_ws4_resident + 7) / 8) * 8 : ((cus * conv_knobs().ws_wg_per_cu) / 8) * 8;
+  return (unsigned)((feat & 8) || total_ids <= resident ? total_ids : resident);  // feat bit 3: one workgroup per tile (A/B aid)
 }
+}  // namespace mi355conv
 
 // Process-wide, host-side setting read at launch time: persistent workgroups of the wave-specialised kernel's next launches (0 = the default, two
 // per CU).  For running independent convs side by side on several streams, each on a share of the chip (tools/bench_conv_concurrent.py).
 extern "C" int mi355_conv_ws4_resident(int wgs) {
   MI355_REQUIRE(wgs >= 0, "conv_ws4_resident: negative count");
-  mi355conv::g_ws4_resident = wgs;
+  g_ws4_resident = wgs;
   return MI355_OK;
 }
 
-bool mi355_conv_ws4_eligible(const mi355_conv_gemm_args& a, bool vec) {
+bool mi355_conv_ws4_eligible(const mi355_conv_gemm_args& a, const int prec, const bool vec) {
   if (!vec || a.Lin <= 0 || a.flat_valid != 0) return false;   // (flattened strided convs: the producers mask by row, not by flat element index)
-  if (a.precision == 5 || a.precision == 6)   // conv mode only (K == 1 layers included), K odd with an even number of tap pairs, 128-column tiles
+  if (prec == 5 || prec == 6)   // conv mode only (K == 1 layers included), K odd with an even number of tap pairs, 128-column tiles
     return a.K % 4 == 3 && 128 + (a.K - 1) * a.dil <= 192 && a.Cout > 64 && !a.pre_fq && (pre_kind(a) == P_NONE || pre_kind(a) == P_LEAKY || pre_kind(a) == P_SNAKE) &&
            epi_family(a) == 0;
   if (!gemm_mode(a) && 128 + (a.K - 1) * a.dil > 192) return false;
-  return a.precision >= 1 && a.precision <= 4 && pre_kind(a) >= 0;
+  return prec >= 1 && prec <= 4 && pre_kind(a) >= 0;
 }
 
 // the timeline probe's buffer: [ceil(grid / 16)][34] uint64 (device memory owned by the caller; nullptr switches the probe off)
@@ -35,25 +50,23 @@ extern "C" int mi355_conv_ws4_debug_buffer(void* p) {
   return MI355_OK;
 }
 
-int mi355_conv_ws4_p2(const mi355_conv_gemm_args& a, hipStream_t st, int feat, unsigned long long* dbg, int bn) {
-  const int pre = pre_kind(a), epi = epi_family(a);
-  const bool gemm = gemm_mode(a);
-  if (bn == 128 && (feat & 4) && pre == P_SNAKE && epi == 0 && !gemm) return launch_ws4<2, P_SNAKE, 0, false, true>(a, st, feat, dbg);
-  if (const int abl = bn == 128 ? feat >> 4 : 0) {  // timing ablations (wrong results by design)
-    if (gemm && epi == 0) {   // GEMM mode (round 6: what bounds the wide linears)
+int mi355_conv_ws4_p2(const ws4_call& c, const int feat) {
+  if (c.bn == 128 && (feat & 4) && c.pre == P_SNAKE && c.epi == 0 && !c.gemm) return route_ws4<2, P_SNAKE, 0, false, true>(c, feat);
+  if (const int abl = c.bn == 128 ? feat >> 4 : 0) {  // timing ablations (wrong results by design)
+    if (c.gemm && c.epi == 0) {   // GEMM mode (round 6: what bounds the wide linears)
       switch (abl) {
-        case 1: return launch_ws4<2, P_NONE, 0, true, false, 1>(a, st, feat & 15);
-        case 4: return launch_ws4<2, P_NONE, 0, true, false, 4>(a, st, feat & 15);
-        case 5: return launch_ws4<2, P_NONE, 0, true, false, 5>(a, st, feat & 15);
+        case 1: return route_ws4<2, P_NONE, 0, true, false, 1>(c, feat & 15);
+        case 4: return route_ws4<2, P_NONE, 0, true, false, 4>(c, feat & 15);
+        case 5: return route_ws4<2, P_NONE, 0, true, false, 5>(c, feat & 15);
       }
     }
-    MI355_REQUIRE(pre == P_SNAKE && epi == 0 && !gemm, "conv_gemm(ws4): ablation tiles exist for the precision-2 Snake kernel and the plain GEMM mode only");
+    MI355_REQUIRE(c.pre == P_SNAKE && c.epi == 0 && !c.gemm, "conv_gemm(ws4): ablation tiles exist for the precision-2 Snake kernel and the plain GEMM mode only");
     switch (abl) {
-      case 1: return launch_ws4<2, P_SNAKE, 0, false, false, 1>(a, st, feat & 15);
-      case 2: return launch_ws4<2, P_SNAKE, 0, false, false, 2>(a, st, feat & 15);
-      case 3: return launch_ws4<2, P_SNAKE, 0, false, false, 3>(a, st, feat & 15);
-      case 4: return launch_ws4<2, P_SNAKE, 0, false, false, 4>(a, st, feat & 15);
-      case 7: return launch_ws4<2, P_SNAKE, 0, false, false, 7>(a, st, feat & 15);
+      case 1: return route_ws4<2, P_SNAKE, 0, false, false, 1>(c, feat & 15);
+      case 2: return route_ws4<2, P_SNAKE, 0, false, false, 2>(c, feat & 15);
+      case 3: return route_ws4<2, P_SNAKE, 0, false, false, 3>(c, feat & 15);
+      case 4: return route_ws4<2, P_SNAKE, 0, false, false, 4>(c, feat & 15);
+      case 7: return route_ws4<2, P_SNAKE, 0, false, false, 7>(c, feat & 15);
     }
     mi355_set_error("conv_gemm(ws4): unknown ablation %d", abl);
     return MI355_ERR_UNSUPPORTED;
@@ -79,15 +92,21 @@ int mi355_conv_ws4_p2(const mi355_conv_gemm_args& a, hipStream_t st, int feat, u
   return MI355_ERR_UNSUPPORTED;
 }
 
-int mi355_conv_ws4_launch(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn) {
-  int rc = MI355_ERR_UNSUPPORTED;
-  if (a.pre_fq) rc = a.precision == 2 ? mi355_conv_ws4_fq(a, st, feat & 3, bn) : MI355_ERR_UNSUPPORTED;
-  else if (a.precision == 2) rc = mi355_conv_ws4_p2(a, st, feat, g_dbg_buffer, bn);
-  else if (a.precision == 4) rc = mi355_conv_ws4_p4(a, st, feat & 3, bn);
-  else if (a.precision == 6) rc = (feat & ~9) ? mi355_conv_ws4_p5_probe(a, st, feat, g_dbg_buffer) : mi355_conv_ws4_p6(a, st, feat & 9, bn);
-  else if (a.precision == 5) rc = (feat & ~11) ? mi355_conv_ws4_p5_probe(a, st, feat, g_dbg_buffer) : mi355_conv_ws4_p5(a, st, feat & 11, bn);
-  else if (a.precision == 1 || a.precision == 3) rc = mi355_conv_ws4_p13(a, st, feat & 3, bn);
-  if (rc == MI355_ERR_UNSUPPORTED)
-    mi355_set_error("conv_gemm(ws4): no instantiation for precision %d, prologue %d, epilogue family %d, %d-column tiles", a.precision, pre_kind(a), epi_family(a), bn);
-  return rc;
+int mi355_conv_ws4_route(const mi355_conv_gemm_args& a, const int prec, const int feat, const int bn, conv_route& r) {
+  const ws4_call c{a, prec, pre_kind(a), epi_family(a), prec != 5 && prec != 6 && gemm_mode(a), bn, r};
+  if (a.pre_fq) return prec == 2 ? mi355_conv_ws4_fq(c, feat & 3) : MI355_ERR_UNSUPPORTED;
+  switch (prec) {
+    case 2: return mi355_conv_ws4_p2(c, feat);
+    case 4: return mi355_conv_ws4_p4(c, feat & 3);
+    case 6: return (feat & ~9) ? mi355_conv_ws4_p5_probe(c, feat) : mi355_conv_ws4_p6(c, feat & 9);
+    case 5: return (feat & ~11) ? mi355_conv_ws4_p5_probe(c, feat) : mi355_conv_ws4_p5(c, feat & 11);
+    case 1:
+    case 3: return mi355_conv_ws4_p13(c, feat & 3);
+  }
+  return MI355_ERR_UNSUPPORTED;
+}
+
+int mi355_conv_ws4_no_instantiation(const mi355_conv_gemm_args& a, const int prec, const int bn) {
+  mi355_set_error("conv_gemm(ws4): no instantiation for precision %d, prologue %d, epilogue family %d, %d-column tiles", prec, pre_kind(a), epi_family(a), bn);
+  return MI355_ERR_UNSUPPORTED;
 }

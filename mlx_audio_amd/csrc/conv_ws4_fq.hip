@@ -4,11 +4,10 @@
 using namespace mi355conv;
 
 #define WS4_FQ(PRE, BNV) \
-  if (bn == BNV && pre == PRE) return launch_ws4<2, PRE, 0, false, false, 0, BNV, true>(a, st, feat)
+  if (c.bn == BNV && c.pre == PRE) return route_ws4<2, PRE, 0, false, false, 0, BNV, true>(c, feat)
 
-int mi355_conv_ws4_fq(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn) {
-  const int pre = pre_kind(a), epi = epi_family(a);
-  if (epi != 0) return MI355_ERR_UNSUPPORTED;
+int mi355_conv_ws4_fq(const ws4_call& c, const int feat) {
+  if (c.epi != 0) return MI355_ERR_UNSUPPORTED;
   WS4_FQ(P_NONE, 128);
   WS4_FQ(P_LEAKY, 128);
   WS4_FQ(P_SNAKE, 128);

@@ -3,10 +3,8 @@
 
 using namespace mi355conv;
 
-int mi355_conv_ws4_p13(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn) {
-  const int pre = pre_kind(a), epi = epi_family(a);
-  const bool gemm = gemm_mode(a);
-  if (a.precision == 1) {
+int mi355_conv_ws4_p13(const ws4_call& c, const int feat) {
+  if (c.prec == 1) {
     WS4_CASE(1, P_NONE, 0);
     WS4_CASE(1, P_LEAKY, 0);
     WS4_CASE(1, P_SNAKE, 0);

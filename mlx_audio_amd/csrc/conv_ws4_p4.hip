@@ -3,9 +3,7 @@
 
 using namespace mi355conv;
 
-int mi355_conv_ws4_p4(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn) {
-  const int pre = pre_kind(a), epi = epi_family(a);
-  const bool gemm = gemm_mode(a);
+int mi355_conv_ws4_p4(const ws4_call& c, const int feat) {
   WS4_CASE(4, P_NONE, 0);
   WS4_CASE(4, P_LEAKY, 0);
   WS4_CASE(4, P_SNAKE, 0);

@@ -4,9 +4,7 @@
 
 using namespace mi355conv;
 
-int mi355_conv_ws4_p6(const mi355_conv_gemm_args& a, hipStream_t st, int feat, int bn) {
-  const int pre = pre_kind(a), epi = epi_family(a);
-  const bool gemm = false;   // K == 1 layers run this kernel in conv mode too (one hi item + one half-empty lo item per chunk)
+int mi355_conv_ws4_p6(const ws4_call& c, const int feat) {
   WS4_CASE(6, P_NONE, 0);
   WS4_CASE(6, P_LEAKY, 0);
   WS4_CASE(6, P_SNAKE, 0);

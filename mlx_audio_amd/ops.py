@@ -661,38 +661,15 @@ def head_gate(x: torch.Tensor, g: torch.Tensor, *, heads: int, dh: int) -> torch
 
 
 # --------------------------------------------------------------------------------------- conv / linear
-def conv_gemm(x: torch.Tensor, pc: PackedConv, y: torch.Tensor, *, dil: int = 1, pad: int = 0,
-              lens_in: Optional[torch.Tensor] = None, lens_out: Optional[torch.Tensor] = None,
-              lout: Optional[int] = None, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-              pre_act: int = ACT_NONE, pre_slope: float = 0.0, pre_alpha: Optional[torch.Tensor] = None,
-              post_act: int = ACT_NONE, post_slope: float = 0.0, res: Optional[torch.Tensor] = None,
-              res_shift: int = 0, out_scale: float = 1.0, accumulate: bool = False,
-              up: Optional[dict] = None, precision: int = 2, tile: int = 0,
-              flat: Optional[dict] = None, use_bias: bool = True, stats: Optional[torch.Tensor] = None,
-              pre_inv_beta: Optional[torch.Tensor] = None, colscale: Optional[torch.Tensor] = None, x_off: int = 0,
-              flatten: bool = False, pre_fq: Optional[torch.Tensor] = None, ext: Optional[torch.Tensor] = None,
-              x_split: bool = False, y_split: bool = False):
-    """y = epilogue(conv1d(prologue(x)))  -- see mi355_conv_gemm_args in the header.
-
-    ``x_split`` / ``y_split``: the float32 tensors ``x`` / ``y`` hold SPLIT words (16-bit hi | lo << 16 of each value in the type of the launch's
-    precision, 2 or 4: ``split16``, ``layernorm(split=...)`` or another launch's ``y_split``) -- the conversion is then done once by the producer
-    instead of once per column tile of this launch.
-
-    ``ext`` ([B, ceil(Lout / 64), Cout, 2] from ``new_ext``): the launch also leaves the per-block, per-channel (min, max) of what it stores, for
-    ``fake_quant_extrema_from_partials`` -- only launches ``conv_ext_supported`` accepts (a quantising prologue on the wave-specialised kernel).
-
-    ``flatten``: the caller states that this is a per-row linear layer (K == 1) whose padding rows (rows >= lens[b]) may be
-    computed and written like any other row (nothing downstream reads them as valid): ``[B, L, C]`` operands whose items are
-    row-contiguous are then handed over as ONE item of B*L rows, so the 128-row tiles are full instead of one partly
-    filled tile per utterance (PL-BERT at T = 80: 62 % -> 100 % useful rows)."""
+def _conv_gemm_args(x, pc, y, dil, pad, lens_in, lens_out, lout, pre, pre_act, pre_slope, pre_alpha, post_act, post_slope, res, res_shift, out_scale, accumulate, up,
+                    precision, tile, flat, use_bias, stats, pre_inv_beta, colscale, x_off, flatten, pre_fq, ext, x_split, y_split):
+    """The ``mi355_conv_gemm_args`` fields of one ``conv_gemm`` call (its arguments, in its order), after the ``flatten`` rewrite."""
     if flatten and pc.k == 1 and up is None and flat is None and res_shift == 0 and stats is None and pre is None and pre_fq is None and x.shape[0] > 1:
         ts = [x, y] + ([res] if res is not None else [])
         if all(t.dim() == 3 and t.shape[:2] == x.shape[:2] and t.stride(0) == t.shape[1] * t.stride(1) for t in ts):
             fl = lambda t: t.as_strided((1, t.shape[0] * t.shape[1], t.shape[2]), (t.shape[0] * t.shape[1] * t.stride(1), t.stride(1), 1))
-            return conv_gemm(fl(x), pc, fl(y), pre_act=pre_act, pre_slope=pre_slope, pre_alpha=pre_alpha, post_act=post_act,
-                             post_slope=post_slope, res=None if res is None else fl(res), out_scale=out_scale, accumulate=accumulate,
-                             precision=precision, tile=tile, use_bias=use_bias, pre_inv_beta=pre_inv_beta, colscale=colscale, x_off=x_off,
-                             x_split=x_split, y_split=y_split)
+            return _conv_gemm_args(fl(x), pc, fl(y), 1, 0, None, None, None, None, pre_act, pre_slope, pre_alpha, post_act, post_slope, None if res is None else fl(res), 0,
+                                   out_scale, accumulate, None, precision, tile, None, use_bias, None, pre_inv_beta, colscale, x_off, False, None, None, x_split, y_split)
     B, Lin, Cx, xbs, ldx = _nlc(x)
     By, Ly, Cy, ybs, ldy = _nlc(y)
     assert B == By
@@ -741,19 +718,66 @@ def conv_gemm(x: torch.Tensor, pc: PackedConv, y: torch.Tensor, *, dil: int = 1,
     if SPLIT_WS_BYTES and B * kw["Lout"] <= 65536:   # only small launches can split: do not even create the scratch for a large batch
         st = _stream()
         kw.update(split_ws=_conv_split_ws(x.device, st).data_ptr(), split_ws_bytes=SPLIT_WS_BYTES)
+    return kw
+
+
+def conv_gemm(x: torch.Tensor, pc: PackedConv, y: torch.Tensor, *, dil: int = 1, pad: int = 0,
+              lens_in: Optional[torch.Tensor] = None, lens_out: Optional[torch.Tensor] = None,
+              lout: Optional[int] = None, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+              pre_act: int = ACT_NONE, pre_slope: float = 0.0, pre_alpha: Optional[torch.Tensor] = None,
+              post_act: int = ACT_NONE, post_slope: float = 0.0, res: Optional[torch.Tensor] = None,
+              res_shift: int = 0, out_scale: float = 1.0, accumulate: bool = False,
+              up: Optional[dict] = None, precision: int = 2, tile: int = 0,
+              flat: Optional[dict] = None, use_bias: bool = True, stats: Optional[torch.Tensor] = None,
+              pre_inv_beta: Optional[torch.Tensor] = None, colscale: Optional[torch.Tensor] = None, x_off: int = 0,
+              flatten: bool = False, pre_fq: Optional[torch.Tensor] = None, ext: Optional[torch.Tensor] = None,
+              x_split: bool = False, y_split: bool = False):
+    """y = epilogue(conv1d(prologue(x)))  -- see mi355_conv_gemm_args in the header.
+
+    ``x_split`` / ``y_split``: the float32 tensors ``x`` / ``y`` hold SPLIT words (16-bit hi | lo << 16 of each value in the type of the launch's
+    precision, 2 or 4: ``split16``, ``layernorm(split=...)`` or another launch's ``y_split``) -- the conversion is then done once by the producer
+    instead of once per column tile of this launch.
+
+    ``ext`` ([B, ceil(Lout / 64), Cout, 2] from ``new_ext``): the launch also leaves the per-block, per-channel (min, max) of what it stores, for
+    ``fake_quant_extrema_from_partials`` -- only launches ``conv_ext_supported`` accepts (a quantising prologue on the wave-specialised kernel).
+
+    ``flatten``: the caller states that this is a per-row linear layer (K == 1) whose padding rows (rows >= lens[b]) may be
+    computed and written like any other row (nothing downstream reads them as valid): ``[B, L, C]`` operands whose items are
+    row-contiguous are then handed over as ONE item of B*L rows, so the 128-row tiles are full instead of one partly
+    filled tile per utterance (PL-BERT at T = 80: 62 % -> 100 % useful rows)."""
+    kw = _conv_gemm_args(x, pc, y, dil, pad, lens_in, lens_out, lout, pre, pre_act, pre_slope, pre_alpha, post_act, post_slope, res, res_shift, out_scale, accumulate, up,
+                         precision, tile, flat, use_bias, stats, pre_inv_beta, colscale, x_off, flatten, pre_fq, ext, x_split, y_split)
     if PROFILE is not None:
         # no host synchronisation here (a .item() on the ragged lengths would drain the queue before every launch: the start event would then
         # be stamped on an idle GPU and the interval would include the host's submission latency); the row count stays a device scalar and
         # profile_finalize() resolves it after the step
-        rows = (kw["Lout"] * B) if lens_out is None else lens_out.sum()
+        rows = (kw["Lout"] * kw["B"]) if kw["lens_out"] is None else lens_out.sum()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         _lib.call_struct("mi355_conv_gemm", "mi355_conv_gemm_args", _stream(), **kw)
         e1.record()
-        PROFILE.append((rows, pc.cin, pc.cout, pc.k, dil, int(res is not None) + int(bool(accumulate)), e0, e1))
+        PROFILE.append((rows, pc.cin, pc.cout, pc.k, kw["dil"], int(res is not None) + int(bool(accumulate)), e0, e1))
         return y
     _lib.call_struct("mi355_conv_gemm", "mi355_conv_gemm_args", _stream(), **kw)
     return y
+
+
+def conv_route(x: torch.Tensor, pc: PackedConv, y: torch.Tensor, *, dil: int = 1, pad: int = 0,
+               lens_in: Optional[torch.Tensor] = None, lens_out: Optional[torch.Tensor] = None,
+               lout: Optional[int] = None, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               pre_act: int = ACT_NONE, pre_slope: float = 0.0, pre_alpha: Optional[torch.Tensor] = None,
+               post_act: int = ACT_NONE, post_slope: float = 0.0, res: Optional[torch.Tensor] = None,
+               res_shift: int = 0, out_scale: float = 1.0, accumulate: bool = False,
+               up: Optional[dict] = None, precision: int = 2, tile: int = 0,
+               flat: Optional[dict] = None, use_bias: bool = True, stats: Optional[torch.Tensor] = None,
+               pre_inv_beta: Optional[torch.Tensor] = None, colscale: Optional[torch.Tensor] = None, x_off: int = 0,
+               flatten: bool = False, pre_fq: Optional[torch.Tensor] = None, ext: Optional[torch.Tensor] = None,
+               x_split: bool = False, y_split: bool = False):
+    """Which kernel ``conv_gemm`` with these arguments runs, and on what geometry: the ``mi355_conv_route`` record of the header as a dict.  Launches
+    nothing; a call ``conv_gemm`` refuses raises the same error."""
+    kw = _conv_gemm_args(x, pc, y, dil, pad, lens_in, lens_out, lout, pre, pre_act, pre_slope, pre_alpha, post_act, post_slope, res, res_shift, out_scale, accumulate, up,
+                         precision, tile, flat, use_bias, stats, pre_inv_beta, colscale, x_off, flatten, pre_fq, ext, x_split, y_split)
+    return _lib.call_struct_out("mi355_conv_gemm_route", "mi355_conv_gemm_args", "mi355_conv_route", **kw)
 
 
 def adain_coef(x: torch.Tensor, gb: Optional[torch.Tensor], lens: Optional[torch.Tensor] = None, eps: float = 1e-5, sums: Optional[torch.Tensor] = None,

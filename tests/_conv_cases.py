@@ -33,7 +33,7 @@ import torch
 SENTINEL = -777.25          # exactly representable; no case produces it
 ENV_KNOBS = ("MI355_CONV_SPLIT", "MI355_CONV_SPLIT_MINSTEPS", "MI355_CONV_FINISH_OLD", "MI355_CONV_NOVEC_FLAT", "MI355_CONV_WS_FEAT", "MI355_CONV_WS_MIN_TILES",
              "MI355_CONV_NO_WS", "MI355_CONV_NO_WS64", "MI355_CONV_WS_WG_PER_CU", "MI355_CONV_SPLIT_WS_MB")   # read once per process: none may be set
-POSTS = {"none": 0, "leaky": 0, "gelu": 1, "silu": 2, "gelu_tanh": 3}       # epi_family (conv_ws4.h:1164)
+POSTS = {"none": 0, "leaky": 0, "gelu": 1, "silu": 2, "gelu_tanh": 3}       # epi_family (conv_ws4.h)
 TILE_CAPS = {1: 1.5e-2, 2: 3e-5, 3: 2e-3, 4: 3e-6, 5: 3e-5, 6: 2e-4}       # the per-tensor bars of tests/test_kernels_gpu.py / test_conv_mx_gpu.py: kept as caps
 G_FORMAT = {1: 2.0 ** -9, 2: 2.0 ** -16, 3: 2.0 ** -12, 4: 2.0 ** -22}
 WS_MIN_TILES = 128
@@ -70,7 +70,7 @@ def ws4_label(prec, mode, pre, epi, bn, fq=False, two_by_two=False):
 def all_ws4_labels():
     out = [ws4_label(p, m, pre, e, bn) for p, lst in WS4_LISTS.items() for m, pre, e, bn in lst]
     out += [ws4_label(2, "conv", p, 0, bn, fq=True) for p, bn in WS4_FQ_LIST]
-    out.append(ws4_label(5, "conv", "SNAKE", 0, 128, two_by_two=True))     # conv_ws4_p5.hip:10, feature digit 2
+    out.append(ws4_label(5, "conv", "SNAKE", 0, 128, two_by_two=True))     # mi355_conv_ws4_p5, feature digit 2
     return out
 
 
@@ -95,11 +95,11 @@ def launch(**kw):
 
 
 def gemm_mode(a):
-    return a["K"] == 1 and a["Cin"] >= 64 and a["pre"] == "NONE" and not a["affine"] and not a["fq"]       # conv_ws4.h:1111
+    return a["K"] == 1 and a["Cin"] >= 64 and a["pre"] == "NONE" and not a["affine"] and not a["fq"]       # gemm_mode (conv_ws4.h)
 
 
 def ws4_eligible(a, prec):
-    """mi355_conv_ws4_eligible (conv_ws4.hip:23-30); flattened strided convs are not part of this suite."""
+    """mi355_conv_ws4_eligible (conv_ws4.hip); flattened strided convs are not part of this suite."""
     if not a["vec"] or a["L"] <= 0:
         return False
     win = 128 + (a["K"] - 1) * a["dil"]
@@ -111,7 +111,7 @@ def ws4_eligible(a, prec):
 
 
 def ws4_facts(a, prec, mode, pre, bn, feat, fq):
-    """The geometry record of launch_ws4 (conv_ws4.h:1114-1156) and the run-time branches the launch's tiles take."""
+    """The geometry route_ws4 decides, the grid ws4_grid sizes at launch time (conv_ws4.h, conv_ws4.hip) and the run-time branches the launch's tiles take."""
     chunks32 = (a["Cin"] + 31) >> 5
     gemm = mode == "gemm"
     nch = (chunks32 + 1) >> 1 if gemm else chunks32
@@ -149,7 +149,7 @@ def ws4_facts(a, prec, mode, pre, bn, feat, fq):
 
 
 def ws4_launch(a, prec, feat, bn):
-    """mi355_conv_ws4_launch and the per-precision lists (conv_ws4.hip:38-93, conv_ws4_{p4,p13,p5,p6,fq}.hip) -> (label, facts) or None (MI355_ERR_UNSUPPORTED)."""
+    """mi355_conv_ws4_route and the per-precision lists (conv_ws4.hip, conv_ws4_{p4,p13,p5,p6,fq}.hip) -> (label, facts) or None (MI355_ERR_UNSUPPORTED)."""
     pre, epi = a["pre"], POSTS.get(a["post"], -1)
     assert feat < 16 and not (prec == 2 and feat & 4) and not (prec == 6 and feat & ~9) and not (prec == 5 and feat & ~11), "ablation / probe builds are not part of this suite"
     if a["fq"]:
@@ -168,7 +168,7 @@ def ws4_launch(a, prec, feat, bn):
 
 
 def split_groups(wgs, nchunks, K, rows_total, Cout, ws_bytes, forced):
-    """split_groups (conv_gemm.hip:520-546) without its knobs."""
+    """split_groups (conv_gemm.hip) without its knobs."""
     if nchunks < 2:
         return 0
     min_chunks = 1 if K >= 4 else (4 + K - 1) // K
@@ -191,18 +191,18 @@ def split_groups(wgs, nchunks, K, rows_total, Cout, ws_bytes, forced):
 
 def _lds_ok(a, prec, bm, bn):
     R = bm + (a["K"] - 1) * a["dil"]
-    return R * 64 * (2 if prec in (2, 4) else 1) + 2 * (bn // 32) * 2048 <= 64 * 1024                     # conv_gemm.hip:257-259
+    return R * 64 * (2 if prec in (2, 4) else 1) + 2 * (bn // 32) * 2048 <= 64 * 1024                     # conv_lds_bytes (conv_gemm.hip)
 
 
 def _split(a, prec, wide, ks):
     if not _lds_ok(a, prec, 64, 128 if wide else 64):
         return "refuse:window too large for LDS", None
-    lean = not a["up_s"] and a["Cout"] % 4 == 0 and a["out_aligned"]                                       # conv_gemm.hip:569-570
+    lean = not a["up_s"] and a["Cout"] % 4 == 0 and a["out_aligned"]                                       # conv_decide's `lean` (conv_gemm.hip)
     return f"splitk/p{prec}/{'64x128' if wide else '64x64'}/" + ("lean" if lean else "general"), dict(groups=ks)
 
 
 def route(a):
-    """mi355_conv_gemm's dispatch (conv_gemm.hip:607-758) -> (label, facts).  facts is the ws4 geometry for a ws4 label, the group count for a split-K
+    """mi355_conv_gemm's dispatch (conv_validate and conv_decide, conv_gemm.hip) -> (label, facts).  facts is the ws4 geometry for a ws4 label, the group count for a split-K
     label, else None.  Labels: ws4/..., 4wave/p<P>/<BM>x<BN>/vec|novec, splitk/p<P>/<tile>/lean|general, each prefixed 'mx->p4 fallback ' when an MX image
     runs the precision-4 arithmetic, or refuse:<reason>."""
     prec = a["precision"] or 2
@@ -299,9 +299,62 @@ def route(a):
     return mx + f"4wave/p{prec}/{bm}x{bn}/vec", None
 
 
+# ----------------------------------------------------------------------------------------------------------------- route() against the library
+PRE_NAMES = ("NONE", "LEAKY", "SNAKE", "SNAKEBETA", "ELU")         # mi355_conv_route.pre
+PRE_ACTS = dict(NONE="ACT_NONE", LEAKY="ACT_LEAKY", SNAKE="ACT_SNAKE", SNAKEBETA="ACT_SNAKE", ELU="ACT_ELU")
+POST_ACTS = dict(none="ACT_NONE", leaky="ACT_LEAKY", gelu="ACT_GELU", silu="ACT_SILU", gelu_tanh="ACT_GELU_TANH")
+ROUTE_GEOMETRY = ("tiles_per_item", "P", "NT", "nch", "R", "fold", "glog", "total_ids", "bn", "feat")
+
+
+def route_args(a, acts):
+    """A ``launch(**kw)`` dict as the keywords of ``mi355_conv_gemm_args`` for ``mi355_conv_gemm_route``, which follows no pointer: the addresses are made
+    up -- 16-byte aligned where the dict says aligned, 4 bytes past that for ``vec=False`` / ``out_aligned=False`` / ``stats_aligned=False``, None where
+    the dict says absent.  ``acts``: where the MI355_ACT_* values come from (``mlx_audio_amd.ops``).  Rows are dense: ld = the channel count rounded up
+    to 4.  The workspace follows the rule of ``ops.conv_gemm`` (B * Lout <= 65536)."""
+    at = lambda n: 0x10000000 + (n << 20)
+    B, L, Lout, Cin, Cout, prec = a["B"], a["L"], a["Lout"], a["Cin"], a["Cout"], a["precision"]
+    ldx, ldy = round_up(Cin, 4), round_up(Cout, 4)
+    snake = a["pre"] in ("SNAKE", "SNAKEBETA")
+    kw = dict(x=at(1) + (0 if a["vec"] else 4), x_bstride=L * ldx, ldx=ldx, x_off=0, Cin=Cin, Lin=L, lens_in=at(2) if a["lens_in"] else None, flat_valid=0, w=at(3), Cout=Cout,
+              K=a["K"], dil=a["dil"], pad=a["pad"], pre_act=getattr(acts, PRE_ACTS[a["pre"]]), pre_slope=0.25, pre_alpha=at(4) if snake else None,
+              pre_inv_beta=at(5) if a["pre"] == "SNAKEBETA" else None, bias=at(6), post_act=getattr(acts, POST_ACTS[a["post"]]), post_slope=0.5, out_scale=1.0,
+              accumulate=int(a["accumulate"]), y=at(7) + (0 if a["out_aligned"] else 4), y_bstride=Lout * ldy, ldy=ldy, Lout=Lout, lens_out=at(8) if a["lens_out"] else None, B=B,
+              precision=prec, tile=a["tile"], post_colscale=at(9) if a["colscale"] else None, x_split=prec if a["x_split"] else 0, y_split=prec if a["y_split"] else 0)
+    if a["affine"]:
+        kw.update(pre_scale=at(10), pre_shift=at(11), pre_ld=round_up(Cin, 32))
+    if a["fq"]:
+        kw.update(pre_fq=at(12))
+    if a["res"]:
+        kw.update(res=at(13), res_bstride=Lout * ldy, ldr=ldy, res_shift=a["res_shift"])
+    if a["up_s"]:
+        kw.update(up_s=a["up_s"], up_p=0, up_cout=Cout // a["up_s"], up_row_off=0, up_Lout=Lout * a["up_s"])
+    if a["stats"]:
+        kw.update(stats_partial=at(14) + (0 if a["stats_aligned"] else 4), stats_bstride=((Lout + 63) // 64) * Cout * 2)
+    if a["split_ws"] and B * Lout <= 65536:
+        kw.update(split_ws=at(15), split_ws_bytes=SPLIT_WS_BYTES)
+    return kw
+
+
+def record_label(r):
+    """A ``mi355_conv_route`` record (dict) in the label format of route()."""
+    mx = "mx->p4 fallback " if r["mx_fallback"] else ""
+    if r["family"] == 2:
+        assert not mx and not r["dbg"] and not r["abl"], r
+        return ws4_label(r["precision"], "gemm" if r["gemm"] else "conv", PRE_NAMES[r["pre"]], r["epi"], r["bn"], fq=bool(r["fq"]), two_by_two=bool(r["two_by_two"]))
+    if r["family"] == 1:
+        return mx + f"splitk/p{r['precision']}/{r['bm']}x{r['bn']}/" + ("lean" if r["lean"] else "general")
+    return mx + f"4wave/p{r['precision']}/{r['bm']}x{r['bn']}/" + ("vec" if r["vec"] else "novec")
+
+
+def polyphase_launches():
+    """The launches of tests/test_conv_kernel_edges_gpu.py::test_polyphase_store_exact as route() sees them."""
+    return [launch(B=2, L=300, Lout=301, Cin=128, Cout=128, K=2, pad=1, pre="LEAKY", res=True, precision=prec, tile=tile, up_s=4, lens_in=[300, 77], lens_out=[301, 78])
+            for prec in (2, 4) for tile in (0, WS, 80000000 + WS, 128128, 2064128)]
+
+
 # ----------------------------------------------------------------------------------------------------------------- the tile scheduler, restated
 def decode_tile(i, P, NT, glog, tpi, lens_out, mutant=None):
-    """decode_tile (conv_ws4.h:60-74): virtual id -> (item, first row, column tile) or None."""
+    """decode_tile (conv_ws4.h): virtual id -> (item, first row, column tile) or None."""
     kq = i >> 3
     ny, pg = kq % NT, kq // NT
     g = glog + 1 if mutant == "glog" else glog
@@ -316,7 +369,7 @@ def decode_tile(i, P, NT, glog, tpi, lens_out, mutant=None):
 
 
 def workgroup_tiles(wg, grid, total_ids, P, NT, glog, tpi, lens_out, mutant=None, table=None):
-    """The tiles one persistent workgroup visits: its first id with work, then next_work until -1 (conv_ws4.h:76-80, 116-119, 483).  ``table``:
+    """The tiles one persistent workgroup visits: its first id with work, then next_work until -1 (conv_ws4.h).  ``table``:
     decode_tile of every id, computed once by the caller (the walk itself stays literal)."""
     dec = (lambda i: table[i]) if table is not None else (lambda i: decode_tile(i, P, NT, glog, tpi, lens_out, mutant))
     out = []
@@ -832,7 +885,7 @@ def float_bound(c, prec):
 
 def in_suite(prec, tile):
     """False for the tile codes that select an ablation or timeline-probe build (wrong by design): a hundred-millions digit, feature bit 2 at precision 2,
-    any feature bit the precision-5 / 6 lists do not carry (conv_ws4.hip:87-88: everything outside 0, 1, 3 at precision 5 and outside 0, 3 at precision 6)."""
+    any feature bit the precision-5 / 6 lists do not carry (mi355_conv_ws4_route: everything outside 0, 1, 3 at precision 5 and outside 0, 3 at precision 6)."""
     code, digit = tile % 10000000, tile // 10000000
     if code != 6128128:
         return True

@@ -15,10 +15,14 @@ mutants, route coverage against the instantiation lists of the sources, the sche
    128- against 64-column ws4 tiles, an item in a ragged batch against the item alone, a second run.
 4. The persistent walk at small shapes under ``mi355_conv_ws4_resident(8 / 16)``, the glog boundaries, refusals, the ws4 fall-through.
 
-What this file cannot see: WHICH kernel a launch ran.  Route coverage rests on ``route()`` of tests/_conv_cases.py predicting the library's dispatch
-(tests/test_conv_refs_cpu.py holds its instantiation lists to the sources, not its control flow): a misprediction would thin the coverage silently, it
-would not fail a test.  The pair "feature digit 8 against 0" is two different launches only at precisions 2, 5 and 6 -- the dispatcher masks that
-bit off at 1, 3 and 4 (``feat & 3``) -- where ``test_persistent_walk_small`` carries the walk-against-one-workgroup-per-tile comparison instead.
+WHICH kernel a launch runs is checked, not predicted: ``run()`` asks the library's own routing function (``ops.conv_route`` -> ``mi355_conv_gemm_route``:
+the validation and decision steps ``mi355_conv_gemm`` itself goes through, then launches from) with the very tensors and keywords of the launch and asserts
+its label and split-K group count against ``route()`` of tests/_conv_cases.py, so a case cannot silently run on another kernel than the one its coverage
+is counted for.  tests/test_conv_refs_cpu.py holds ``route()`` to the same function on the CPU for every launch of the case tables (ws4 geometry included)
+and its instantiation lists to the sources.  What stays unseen from here: the grid of a ws4 launch, sized at launch time from the CU count and
+``mi355_conv_ws4_resident`` (``test_persistent_walk_small`` compares its effect).  The pair "feature digit 8 against 0" is two different launches only at
+precisions 2, 5 and 6 -- the dispatcher masks that bit off at 1, 3 and 4 (``feat & 3``) -- where ``test_persistent_walk_small`` carries the
+walk-against-one-workgroup-per-tile comparison instead.
 
 The library's A/B knobs are read once per process: none may be set (asserted at import)."""
 import os
@@ -128,6 +132,9 @@ def run(ops, c, prec, tile, only=None, extra=None):
     if d["fq"] is not None:
         kw.update(pre_fq=d["fq"][sl].contiguous())
     kw.update(extra or {})
+    rec = ops.conv_route(d["x"][sl], pc, y, **kw)        # a host call: which kernel the library runs for exactly this launch
+    lab, facts = S.route(S.case_launch(c, prec, tile, only=only))
+    assert S.record_label(rec) == lab and rec["groups"] == (facts["groups"] if "splitk/" in lab else 0), (S.case_id(c), prec, tile, only, lab, rec)
     ops.conv_gemm(d["x"][sl], pc, y, **kw)
     torch.cuda.synchronize()
     out = buf.cpu()
@@ -369,7 +376,7 @@ def test_refusals_leave_outputs_untouched(ops, monkeypatch):
 
 @pytest.mark.parametrize("prec", [1, 3])
 def test_ws4_unsupported_falls_through_to_the_4wave_route(ops, prec):
-    """An ELU prologue has no precision-1 / 3 ws4 instantiation: tile 0 with >= 128 tiles takes mi355_conv_ws4_launch's MI355_ERR_UNSUPPORTED and must land
+    """An ELU prologue has no precision-1 / 3 ws4 instantiation: tile 0 with >= 128 tiles takes mi355_conv_ws4_route's MI355_ERR_UNSUPPORTED and must land
     on the 4-wave kernel route() names, with the right result and no error left behind.  Strictly positive integers: ELU is the identity on them, so the
     result is exact."""
     g = torch.Generator().manual_seed(9)

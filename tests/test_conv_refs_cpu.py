@@ -1,6 +1,7 @@
 """Everything about the conv-kernel suite that can be checked without a GPU (tests/_conv_cases.py; the GPU half is tests/test_conv_kernel_edges_gpu.py):
 the statements against torch's own conv1d, the exactness preconditions of the exact cases (the CPU proof that a GPU mismatch is the kernel's), the mutants,
-route coverage against the instantiation lists parsed from the sources, the claimed branch facts, and the tile scheduler."""
+route coverage against the instantiation lists parsed from the sources, route() against the library's own routing function (``mi355_conv_gemm_route``, which
+needs no device) launch by launch, the claimed branch facts, and the tile scheduler."""
 import os
 import re
 
@@ -188,18 +189,23 @@ def _parse_ws4_lists():
                 labels.append(S.ws4_label(int(a[0]), "conv", a[1][2:], int(a[2]), 64 if kind.endswith("N64") else 128))
             else:
                 labels.append(S.ws4_label(int(a[0]), "gemm", "NONE", int(a[1]), 64 if kind.endswith("N64") else 128))
-        for m in re.finditer(r"return launch_ws4<5, P_SNAKE, 0, false, false, 0, 128, false, false>", text):
+        for m in re.finditer(r"return route_ws4<5, P_SNAKE, 0, false, false, 0, 128, false, false>", text):
             labels.append(S.ws4_label(5, "conv", "SNAKE", 0, 128, two_by_two=True))
     return labels
 
 
 def _parse_4wave():
+    """The one list of 4-wave / split-K instantiations (launcher_of<PREC>, conv_gemm.hip) times the precisions of its dispatch."""
     text = open(os.path.join(CSRC, "conv_gemm.hip")).read()
-    body = text[text.index('extern "C" int mi355_conv_gemm('):]
-    out = [f"4wave/p{p}/{bm}x{bn}/{'vec' if v == 'true' else 'novec'}" for bm, bn, p, v in re.findall(r"return launch<(\d+), (\d+), (\d), (true|false)>\(a, st\);", body)]
-    precs = re.findall(r"return launch_split<BM, BN, (\d)>\(a, st, ks\);", text)
-    tiles = set(re.findall(r"launch_split_p<(\d+), (\d+)>\(a, st, ks\)", body))
-    out += [f"splitk/p{p}/{bm}x{bn}" for p in precs for bm, bn in tiles]
+    body = text[text.index("conv_launch_fn launcher_of(const conv_route& r) {\n  const int tile"):text.index("// The tile code, decoded once.")]
+    precs = re.findall(r"return launcher_of<(\d)>\(r\);", body)
+    no_novec = re.findall(r"if constexpr \(PREC != (\d)\) return launch<64, 64, PREC, false>;", body)
+    assert len(precs) == 4 and len(no_novec) == 1
+    out = []
+    for bm, bn, v in re.findall(r"return launch<(\d+), (\d+), PREC, (true|false)>;", body):
+        out += [f"4wave/p{p}/{bm}x{bn}/{'vec' if v == 'true' else 'novec'}" for p in precs if v == "true" or p not in no_novec]
+    for bm, bn in re.findall(r"launch_split<(\d+), (\d+), PREC>", body):
+        out += [f"splitk/p{p}/{bm}x{bn}" for p in precs]
     return out
 
 
@@ -230,23 +236,83 @@ def test_every_instantiation_is_reached():
     assert any(l.startswith("mx->p4 fallback 4wave") for l in seen) and any(l.startswith("mx->p4 fallback splitk") for l in seen)
 
 
-def test_window_limit_and_fallthrough_routes():
+def _window_limit_launches():
     win196 = next(c for c in EXACT if c["name"] == "k5 d17 window 196")
+    d = {("win196", prec, tile): S.case_launch(win196, prec, tile) for prec in (1, 2, 3, 4) for tile in (S.WS, S.WS64)}
+    d["tile 0 window 196"] = S.launch(B=130, L=5, Cin=64, Cout=128, K=5, dil=17, pad=34, split_ws=False)
+    d["elu p1"] = S.launch(B=130, L=5, Cin=64, Cout=128, K=3, pad=1, pre="ELU", precision=1, split_ws=False)
+    d["ws4 p2"] = S.launch(B=130, L=5, Cin=64, Cout=128, K=3, pad=1, precision=2)
+    d["ws4 p3 thin"] = S.launch(B=130, L=5, Cin=64, Cout=64, K=3, pad=1, precision=3)
+    d["mx ws64"] = S.launch(Cin=64, Cout=128, K=3, precision=5, tile=S.WS64, L=200)
+    d["splitk no workspace"] = S.launch(Cin=64, Cout=128, K=3, tile=2064128, L=200, split_ws=False)
+    return d
+
+
+def test_window_limit_and_fallthrough_routes():
+    d = _window_limit_launches()
     for prec in (1, 2, 3, 4):
-        assert S.route(S.case_launch(win196, prec, S.WS))[0].startswith("refuse:the wave-specialised tile")
-        assert S.route(S.case_launch(win196, prec, S.WS64))[0].startswith("refuse:the wave-specialised tile")
+        assert S.route(d["win196", prec, S.WS])[0].startswith("refuse:the wave-specialised tile")
+        assert S.route(d["win196", prec, S.WS64])[0].startswith("refuse:the wave-specialised tile")
     # tile 0 with >= 128 tiles and a window past the limit: a 4-wave launch
-    a = S.launch(B=130, L=5, Cin=64, Cout=128, K=5, dil=17, pad=34, split_ws=False)
-    assert S.route(a)[0] == "4wave/p2/64x128/vec"
+    assert S.route(d["tile 0 window 196"])[0] == "4wave/p2/64x128/vec"
     # the ws4 MI355_ERR_UNSUPPORTED fall-through: an ELU prologue at precision 1 has no instantiation -> the 4-wave kernel tile 0 names
-    a = S.launch(B=130, L=5, Cin=64, Cout=128, K=3, pad=1, pre="ELU", precision=1, split_ws=False)
+    a = d["elu p1"]
     assert S.ws4_eligible(a, 1) and S.ws4_launch(a, 1, 0, 128) is None and S.route(a)[0] == "4wave/p1/64x128/vec"
-    a = S.launch(B=130, L=5, Cin=64, Cout=128, K=3, pad=1, precision=2)
-    assert S.route(a)[0] == "ws4/p2/conv/NONE/epi0/bn128"
-    a = S.launch(B=130, L=5, Cin=64, Cout=64, K=3, pad=1, precision=3)
-    assert S.route(a)[0] == "ws4/p3/conv/NONE/epi0/bn64"
-    assert S.route(S.launch(Cin=64, Cout=128, K=3, precision=5, tile=S.WS64, L=200))[0].startswith("refuse:MX images")
-    assert S.route(S.launch(Cin=64, Cout=128, K=3, tile=2064128, L=200, split_ws=False))[0].startswith("refuse:the split-K tiles")
+    assert S.route(d["ws4 p2"])[0] == "ws4/p2/conv/NONE/epi0/bn128"
+    assert S.route(d["ws4 p3 thin"])[0] == "ws4/p3/conv/NONE/epi0/bn64"
+    assert S.route(d["mx ws64"])[0].startswith("refuse:MX images")
+    assert S.route(d["splitk no workspace"])[0].startswith("refuse:the split-K tiles")
+
+
+def _suite_launches():
+    """Every launch of the GPU suite's case tables as route() sees it -- each case at each of its precisions on each tile code in_suite admits, the whole
+    batch and each item alone -- plus the launches of test_window_limit_and_fallthrough_routes and of the GPU suite's test_polyphase_store_exact."""
+    for c in S.all_cases():
+        for prec in c["precs"]:
+            for tile in (c["tiles"] or S.EVERY):
+                if S.in_suite(prec, tile):
+                    for only in [None] + list(range(c["B"])):
+                        yield (S.case_id(c), prec, tile, only), S.case_launch(c, prec, tile, only=only)
+    for key, a in _window_limit_launches().items():
+        yield key, a
+    for a in S.polyphase_launches():
+        yield ("polyphase", a["precision"], a["tile"]), a
+
+
+def test_route_is_the_librarys_routing_function_launch_by_launch(capsys):
+    """route() of tests/_conv_cases.py against ``mi355_conv_gemm_route`` on every launch of ``_suite_launches``: where route() names a kernel the library
+    returns 0 and its record formats to exactly that label, with the split-K group count and the ws4 geometry of route()'s facts; where route() refuses,
+    the library refuses and leaves the record alone.  The environment knobs must be unset (route() restates the defaults)."""
+    import ctypes
+
+    from mlx_audio_amd import _lib, ops
+
+    assert [k for k in S.ENV_KNOBS if k in os.environ] == []
+    lib = _lib.load()
+    fields = [f for f, _ in _lib._STRUCT_DECLS["mi355_conv_route"]]
+    n = refused = 0
+    for key, a in _suite_launches():
+        label, facts = S.route(a)
+        args = _lib.STRUCTS["mi355_conv_gemm_args"](**{k: v for k, v in S.route_args(a, ops).items() if v is not None})
+        out = _lib.STRUCTS["mi355_conv_route"](**{f: -1 for f in fields})
+        rc = lib.mi355_conv_gemm_route(ctypes.byref(args), ctypes.byref(out))
+        rec = {f: getattr(out, f) for f in fields}
+        n += 1
+        if label.startswith("refuse:"):
+            refused += 1
+            assert rc != 0 and lib.mi355_last_error() and all(v == -1 for v in rec.values()), (key, label, rc, rec)
+            continue
+        assert rc == 0, (key, label, rc, lib.mi355_last_error())
+        assert S.record_label(rec) == label, (key, label, rec)
+        if label.startswith("splitk/") or label.startswith("mx->p4 fallback splitk/"):
+            assert rec["groups"] == facts["groups"], (key, label, rec, facts)
+        elif label.startswith("ws4/"):
+            assert {f: rec[f] for f in S.ROUTE_GEOMETRY} == {f: facts[f] for f in S.ROUTE_GEOMETRY}, (key, label, rec, facts)
+        else:
+            assert facts is None
+    with capsys.disabled():
+        print(f"\nCONV route: {n} launches compared with mi355_conv_gemm_route ({refused} of them refusals), 0 left out")
+    assert n > 40000
 
 
 @pytest.mark.parametrize("c", S.all_cases(), ids=S.case_id)
@@ -307,7 +373,7 @@ def test_scheduler_visits_every_tile_once():
 
 @pytest.mark.parametrize("P", [1, 7, 9] + list(S.GLOG_P) + [2100])
 def test_scheduler_literal_walk(P):
-    """The literal next_work walk of every workgroup, for EVERY grid size 8 .. 512 in steps of 8 (as launch_ws4 clamps it to the id count) and NT 1 .. 4,
+    """The literal next_work walk of every workgroup, for EVERY grid size 8 .. 512 in steps of 8 (as ws4_grid clamps it to the id count) and NT 1 .. 4,
     at every glog boundary of P: each live tile exactly once over all workgroups, a workgroup's ids all on its own XCD, ragged items whose dead tiles
     (and one empty item) are skipped."""
     tpi = 3 if P % 3 == 0 else 1
