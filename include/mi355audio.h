@@ -1722,6 +1722,90 @@ typedef struct {
 } mi355_qformer_windows_args;
 int mi355_qformer_windows(const mi355_qformer_windows_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixture-of-experts FFN (lm/moe.py): the Ling / Ming router, a counting sort of the (token, slot) pairs by expert, and the routed expert
+ * GLU as a grouped GEMM on the matrix pipe (moe.hip).  Entry points added to ABI 37 (new structs and functions only; no existing layout
+ * changed).  Nothing is allocated; no floating-point atomics, no persistent or spinning kernels: every loop is bounded by a size read once.
+ * Every sum runs in a fixed order, so two calls on the same bytes give the same bits and a token's output does not depend on which other
+ * tokens share the call.  A call that is refused (MI355_ERR_ARG / MI355_ERR_UNSUPPORTED) launches nothing and leaves every output untouched.
+ * ------------------------------------------------------------------------------------------ */
+#define MI355_MOE_MAX_EXPERTS 512
+#define MI355_MOE_MAX_TOPK 16
+#define MI355_MOE_TILE_ROWS 32    /* rows of one tile of the grouped GEMM: the M of one v_mfma_f32_32x32x16_bf16 */
+#define MI355_MOE_COL_TILE 64     /* output columns of one workgroup: two waves of 32 columns, times two K groups */
+enum { MI355_MOE_SOFTMAX = 0, MI355_MOE_SIGMOID = 1 };
+
+/* group_expert_select (bailing_moe.py:163-200) on router logits [N, ld >= E] -> ids [N, k] int32, weights [N, k] float32, both contiguous.
+ *   score  = softmax(logits) or sigmoid(logits), float32;   sel = score + expert_bias (nullable, [E]): used for the selection only
+ *   n_group > 1: group g = experts [g E / n_group, (g + 1) E / n_group); its score is the sum of its two largest sel; the
+ *                n_group - topk_group groups of lowest score get sel = 0.0 for all their experts (0.0, not -inf, as the reference does: a
+ *                zeroed expert still beats a kept one whose biased score is negative)
+ *   ids    = the k experts of largest sel, written in DESCENDING sel; weights = score[ids] (unbiased), divided by (their sum in slot order
+ *            + 1e-20) when k > 1 and norm_topk_prob, then multiplied by routed_scaling_factor.
+ * Exact ties go to the LOWER index, among experts and among groups (of two groups with equal score the higher-numbered one is zeroed first).
+ * The reference's argpartition leaves both the order of the k ids and the winner of a tie unspecified; this is one of its admissible results.
+ * One wavefront per token.  1 <= k <= min(E, MI355_MOE_MAX_TOPK), E <= MI355_MOE_MAX_EXPERTS, else MI355_ERR_UNSUPPORTED; n_group >= 1 must
+ * divide E with at least two experts per group when n_group > 1, n_group <= 64, 1 <= topk_group <= n_group, else MI355_ERR_ARG. */
+typedef struct {
+  const float* logits; int64_t ld; int32_t N; int32_t E; int32_t k;
+  const float* expert_bias;
+  int32_t score_fn; int32_t n_group; int32_t topk_group; int32_t norm_topk_prob; float routed_scaling_factor;
+  int32_t* ids; float* weights;
+} mi355_moe_route_args;
+int mi355_moe_route(const mi355_moe_route_args* a, void* stream);
+
+/* The caller-supplied workspace of mi355_moe_plan / mi355_moe_glu for N tokens, k slots, E experts and widths D (model) / I (expert):
+ * byte offsets of { h [N k, I] f32, y [N k, D] f32, counts [E] i32, offsets [E + 1] i32, perm [N k] i32, tiles [max_tiles, 4] i32 } and the
+ * total in layout[0 .. 6], max_tiles = ceil(N k / MI355_MOE_TILE_ROWS) + E in layout[7].  mi355_moe_workspace_bytes returns layout[6]
+ * (-1 on bad sizes).  The base must be 16-byte aligned. */
+int64_t mi355_moe_workspace_bytes(int32_t N, int32_t k, int32_t E, int32_t D, int32_t I);
+int mi355_moe_workspace_layout(int32_t N, int32_t k, int32_t E, int32_t D, int32_t I, int64_t* layout);
+
+/* Counting sort of the N k pairs p = token * k + slot by expert ids[p] (values outside [0, E) are clamped into it), into the workspace:
+ * counts[e], offsets[e] = sum of the counts below e (offsets[E] = N k), perm[offsets[e] + j] = the j-th pair of expert e in ascending p
+ * (stable), and the tile list: for every expert in order, ceil(counts[e] / TILE) records (expert, first sorted row, rows <= TILE, 0); the
+ * remaining records up to max_tiles have rows = 0, so the GEMM grid is sized on the host and surplus workgroups exit.  Two launches: one
+ * workgroup counts (integer LDS atomics), scans and writes the tiles; one wave per expert then places its pairs by ballot prefix.
+ * Scaling: the first launch is ONE workgroup over all N k ids and every expert's wave rescans all of them, O(E N k) reads in all: 11 us up
+ * to 3072 pairs at E = 64, 95 us at 24 576 (measured); sized for decode steps and prefill chunks of a few thousand tokens, not for the 2^28
+ * pairs the workspace arithmetic admits. */
+typedef struct {
+  const int32_t* ids; int32_t N; int32_t k; int32_t E; int32_t D; int32_t I;
+  void* workspace; int64_t workspace_bytes;
+} mi355_moe_plan_args;
+int mi355_moe_plan(const mi355_moe_plan_args* a, void* stream);
+
+/* Expert weight images.  w [E, Ncols, Kdim] float32 on the device (the reference's SwitchLinear layout: y = x @ w[e]^T) -> bf16 hi + lo
+ * images in B-fragment order: element ((((e NT + nt) KS + ks) 2 + img) 64 + lane) 8 + j  <-  part img (0 = bf16(w), 1 = bf16(w - hi)) of
+ * w[e, n = nt 32 + lane % 32, kk = ks 16 + (lane / 32) 8 + j], zero outside the matrix; NT = ceil(Ncols / 32), KS = ceil(Kdim / 16).  A wave
+ * that owns column tile nt of expert e streams KS contiguous 2 KiB records.  mi355_moe_image_elems returns the element count (-1 on bad sizes). */
+int64_t mi355_moe_image_elems(int32_t E, int32_t Ncols, int32_t Kdim);
+int mi355_moe_pack(const float* w, int32_t E, int32_t Ncols, int32_t Kdim, uint16_t* image, void* stream);
+
+/* SwitchGLU (switch_layers.py) behind mi355_moe_plan, and the weighted combine.  mode 0, three launches:
+ *   1. per tile: the tile's token rows of x [N, ldx >= D] gathered through perm, split to bf16 hi + lo and staged in LDS in A-fragment order,
+ *      times the gate and up images of the tile's expert ([D, I] each) on v_mfma_f32_32x32x16_bf16 with the hi.hi, hi.lo and lo.hi products;
+ *      h[r] = silu(gate + b_gate[e]) * (up + b_up[e]) in sorted order                                  (h [N k, I] in the workspace)
+ *   2. per tile: h rows times the down image [I, D] + b_down[e], written to y [N k, D] at row perm[r] (pair order)
+ *   3. out[t] = sum_slot weights[t, slot] * y[t k + slot] (an fmaf chain in slot order) + shared[t] + res[t]   (both nullable, added in
+ *      that order)
+ * The grid of 1 and 2 is max_tiles x ceil(columns / MI355_MOE_COL_TILE) workgroups of four waves: wave (cw, kg) owns 32 columns and one half of
+ * every 128-wide K chunk; the two K groups are joined through LDS, group 0 + group 1.  The biases are [E, I], [E, I], [E, D] (nullable).
+ * mode 1 (one launch, for tests and plain SwitchLinear): out[t k + slot] = x[t] @ w_gate[e]^T + b_gate[e] with the image w_gate of
+ * [E, Ncols = I, Kdim = D]; out is [N k, ldo >= I], the other images, weights, shared and res are ignored.
+ * D and I multiples of 4, rows 16-byte aligned (strides multiples of 4), else MI355_ERR_ARG; so is a workspace shorter than
+ * mi355_moe_workspace_bytes.  The workspace must hold the plan of the same (N, k, E, D, I). */
+typedef struct {
+  const float* x; int64_t ldx; int32_t N; int32_t k; int32_t E; int32_t D; int32_t I;
+  const uint16_t* w_gate; const uint16_t* w_up; const uint16_t* w_down;
+  const float* b_gate; const float* b_up; const float* b_down;
+  const float* weights;
+  const float* shared; int64_t ld_shared; const float* res; int64_t ld_res;
+  float* out; int64_t ldo;
+  void* workspace; int64_t workspace_bytes; int32_t mode;
+} mi355_moe_glu_args;
+int mi355_moe_glu(const mi355_moe_glu_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

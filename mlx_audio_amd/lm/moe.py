@@ -1,0 +1,319 @@
+"""The sparse mixture-of-experts FFN of the Ling / Ming language models (lm/models/bailing_moe.py, switch_layers.py of the reference) on the
+device: the router's ``gate_proj`` and the shared experts run on the existing ``linear`` + ``swiglu``; routing, the sort by expert, the routed
+``SwitchGLU`` and the weighted combine are the kernels of csrc/moe.hip (``ops.moe_route`` / ``ops.switch_glu``).
+
+Parameter names and ``ModelArgs`` fields are the reference's.  ``BailingMoeModel`` / ``Model`` are a host schedule on existing kernels (``rmsnorm``,
+``linear``, ``head_norm_rope`` / ``partial_rope``, ``flash_attention`` over a ``KVCache``, ``embed_sum``): token ids -> logits for prefill and
+one-row decode steps.  NOT built (each raises by name): quantised experts, hub download, head widths other than 64 / 128, ``rope_scaling``."""
+from __future__ import annotations
+
+from dataclasses import dataclass, fields
+from typing import Dict, List, Optional, Union
+
+import torch
+
+from .. import ops
+from .stack import KVCache, linear, make_lin
+
+
+@dataclass
+class ModelArgs:
+    model_type: str
+    hidden_size: int
+    intermediate_size: int
+    max_position_embeddings: int
+    moe_intermediate_size: int
+    num_experts: int
+    num_shared_experts: int
+    norm_topk_prob: bool
+    num_attention_heads: int
+    num_experts_per_tok: int
+    num_hidden_layers: int
+    num_key_value_heads: int
+    rms_norm_eps: float
+    rope_theta: float
+    vocab_size: int
+    first_k_dense_replace: int
+    rope_scaling: Optional[Dict[str, Union[float, str]]] = None
+    use_bias: bool = False
+    use_qkv_bias: bool = False
+    norm_head: bool = False
+    norm_softmax: bool = False
+    use_qk_norm: bool = False
+    tie_word_embeddings: bool = False
+    partial_rotary_factor: float = 1.0
+    rotary_dim: Optional[int] = None
+    moe_router_enable_expert_bias: bool = False
+    moe_router_enable_routed_scaling: bool = True
+    routed_scaling_factor: float = 1.0
+    score_function: str = "softmax"
+    n_group: int = 1
+    topk_group: int = 4
+    moe_shared_expert_intermediate_size: Optional[int] = None
+    moe_router_enable_shared_expert: bool = True
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "ModelArgs":
+        names = {f.name for f in fields(cls)}
+        a = cls(**{k: v for k, v in d.items() if k in names})
+        if a.rope_scaling is not None:
+            raise NotImplementedError("bailing_moe: rope_scaling is not built")
+        if a.hidden_size // a.num_attention_heads not in (64, 128):
+            raise NotImplementedError(f"bailing_moe: head width {a.hidden_size // a.num_attention_heads} is not built (64 or 128)")
+        if a.score_function not in ops.MOE_SCORE_FN:
+            raise ValueError(f"bailing_moe: unknown score_function {a.score_function!r}")
+        return a
+
+
+def from_pretrained(*_, **__):
+    raise NotImplementedError("bailing_moe: hub download is not built; load a local checkpoint and pass its tensors")
+
+
+def sanitize(weights: Dict[str, torch.Tensor], args: ModelArgs) -> Dict[str, torch.Tensor]:
+    """``Model.sanitize`` of the reference: per-expert tensors stacked into ``switch_mlp.*``, the router renamed to ``gate.gate_proj.*``, the tied
+    head dropped, ``norm_head`` applied.  Quantised checkpoints (``.scales`` / ``.biases`` beside an expert weight) are refused by name."""
+    w = dict(weights)
+    if any(k.endswith((".scales", ".biases")) and ".mlp." in k for k in w):
+        raise NotImplementedError("bailing_moe: quantised experts (QuantizedSwitchLinear) are not built")
+    if args.tie_word_embeddings:
+        w.pop("lm_head.weight", None)
+    if args.norm_head and "lm_head.weight" in w:
+        h = w["lm_head.weight"].float()
+        w["lm_head.weight"] = h / (torch.linalg.norm(h, dim=0, keepdim=True) + 1e-7)
+    for l in range(args.first_k_dense_replace, args.num_hidden_layers):
+        p = f"model.layers.{l}.mlp"
+        for m in ("gate_proj", "down_proj", "up_proj"):
+            for k in ("weight", "bias"):
+                if f"{p}.experts.0.{m}.{k}" in w:
+                    w[f"{p}.switch_mlp.{m}.{k}"] = torch.stack([w.pop(f"{p}.experts.{e}.{m}.{k}") for e in range(args.num_experts)])
+        for k in ("weight", "bias"):
+            if f"{p}.gate.{k}" in w:
+                w[f"{p}.gate.gate_proj.{k}"] = w.pop(f"{p}.gate.{k}")
+    return w
+
+
+class SwitchGLU:
+    """``switch_mlp.{gate,up,down}_proj``: the packed expert images.  ``__call__`` is the routed FFN with its combine (``ops.switch_glu``)."""
+
+    def __init__(self, weights, prefix: str, device):
+        if f"{prefix}gate_proj.scales" in weights:
+            raise NotImplementedError("bailing_moe: quantised experts (QuantizedSwitchLinear) are not built")
+        g = lambda n: weights.get(f"{prefix}{n}")
+        self.experts = ops.PackedExperts.pack(g("gate_proj.weight"), g("up_proj.weight"), g("down_proj.weight"), device, gate_b=g("gate_proj.bias"),
+                                              up_b=g("up_proj.bias"), down_b=g("down_proj.bias"))
+
+    def __call__(self, x, ids, weights, out, *, shared=None, res=None):
+        return ops.switch_glu(x, self.experts, ids, weights, out, shared=shared, res=res)
+
+
+class BailingMoeGate:
+    def __init__(self, args: ModelArgs, weights, prefix: str, device):
+        self.args = args
+        self.lin = make_lin(weights[f"{prefix}gate_proj.weight"], weights.get(f"{prefix}gate_proj.bias"), device)
+        b = weights.get(f"{prefix}expert_bias") if args.moe_router_enable_expert_bias else None
+        self.expert_bias = None if b is None else b.to(device=device, dtype=torch.float32).contiguous()
+
+    def __call__(self, x: torch.Tensor):
+        """x [B, L, D] -> (ids [B L, k] int32, weights [B L, k])."""
+        a = self.args
+        B, L, _ = x.shape
+        logits = torch.empty(B, L, a.num_experts, device=x.device)
+        linear(x, self.lin, logits)
+        return ops.moe_route(logits.view(B * L, a.num_experts), a.num_experts_per_tok, expert_bias=self.expert_bias, score_function=a.score_function,
+                             n_group=a.n_group, topk_group=a.topk_group, norm_topk_prob=a.norm_topk_prob, routed_scaling_factor=a.routed_scaling_factor)
+
+
+class BailingMoeMLP:
+    """down(swiglu(gate(x), up(x))) on the dense kernels: gate and up rows interleaved into one image for ``ops.swiglu``."""
+
+    def __init__(self, weights, prefix: str, device):
+        wg, wu = weights[f"{prefix}gate_proj.weight"], weights[f"{prefix}up_proj.weight"]
+        bg, bu = weights.get(f"{prefix}gate_proj.bias"), weights.get(f"{prefix}up_proj.bias")
+        self.inter = wg.shape[0]
+        inter = lambda a, b: torch.stack([a, b], 1).reshape(2 * a.shape[0], *a.shape[1:])
+        self.gate_up = make_lin(inter(wg, wu), None if bg is None else inter(bg, bu), device)
+        self.down = make_lin(weights[f"{prefix}down_proj.weight"], weights.get(f"{prefix}down_proj.bias"), device)
+
+    def __call__(self, x: torch.Tensor, out: torch.Tensor, *, res: Optional[torch.Tensor] = None):
+        B, L, _ = x.shape
+        gu = torch.empty(B, L, 2 * self.inter, device=x.device)
+        h = torch.empty(B, L, self.inter, device=x.device)
+        linear(x, self.gate_up, gu)
+        ops.swiglu(gu, h)
+        return linear(h, self.down, out, res=res)
+
+
+class BailingMoeSparseMoeBlock:
+    def __init__(self, args: ModelArgs, weights, prefix: str, device):
+        self.args = args
+        self.switch_mlp = SwitchGLU(weights, f"{prefix}switch_mlp.", device)
+        self.gate = BailingMoeGate(args, weights, f"{prefix}gate.", device)
+        on = args.num_shared_experts > 0 and args.moe_router_enable_shared_expert
+        self.shared_experts = BailingMoeMLP(weights, f"{prefix}shared_experts.", device) if on else None
+
+    def __call__(self, x: torch.Tensor, out: torch.Tensor, *, res: Optional[torch.Tensor] = None, trace: Optional[dict] = None):
+        """x / out / res [B, L, D]: out = sum_slot weight * expert(x) + shared_experts(x) + res."""
+        B, L, D = x.shape
+        ids, wts = self.gate(x)
+        shared = None
+        if self.shared_experts is not None:
+            shared = self.shared_experts(x, torch.empty(B, L, D, device=x.device)).view(B * L, D)
+        if trace is not None:
+            trace.update(ids=ids, weights=wts, shared=shared)
+        self.switch_mlp(x.reshape(B * L, D), ids, wts, out.view(B * L, D), shared=shared, res=None if res is None else res.reshape(B * L, D))
+        return out
+
+
+class _Attention:
+    """``BailingMoeAttention``: the fused ``query_key_value`` image split at load into q and k | v (the cache row's own layout).  nn.RoPE pairs
+    channel i with i + rot / 2; on ``rot < head_dim`` the kernel at hand (``partial_rope``) pairs 2i with 2i + 1, so the q / k rows (and the q / k
+    norm weights) are permuted inside every head at load: q . k does not change under one permutation of both."""
+
+    def __init__(self, args: ModelArgs, weights, prefix: str, device):
+        H, G = args.num_attention_heads, args.num_key_value_heads
+        dh = args.hidden_size // H
+        self.H, self.G, self.dh, self.eps = H, G, dh, args.rms_norm_eps
+        self.rot = args.rotary_dim if args.rotary_dim is not None else int(dh * args.partial_rotary_factor)
+        src = torch.arange(dh)
+        if self.rot < dh:
+            src[0:self.rot:2], src[1:self.rot:2] = torch.arange(self.rot // 2), torch.arange(self.rot // 2, self.rot)
+        rows = lambda n: (torch.arange(n)[:, None] * dh + src[None, :]).reshape(-1)
+        w, b = weights[f"{prefix}query_key_value.weight"], weights.get(f"{prefix}query_key_value.bias")
+        pick = torch.cat([rows(H), H * dh + rows(G), (H + G) * dh + torch.arange(G * dh)])
+        w, b = w[pick], None if b is None else b[pick]
+        self.wq = make_lin(w[:H * dh], None if b is None else b[:H * dh], device)
+        self.wkv = make_lin(w[H * dh:], None if b is None else b[H * dh:], device)
+        self.dense = make_lin(weights[f"{prefix}dense.weight"], weights.get(f"{prefix}dense.bias"), device)
+        nw = lambda n: weights[f"{prefix}{n}_layernorm.weight"][src].to(device=device, dtype=torch.float32).contiguous() if args.use_qk_norm else None
+        self.qn, self.kn = nw("query"), nw("key")
+        self.cos, self.sin = ops.moonshine_rope_tables(self.rot, args.max_position_embeddings, base=args.rope_theta, device=device)
+
+    def __call__(self, h: torch.Tensor, x: torch.Tensor, kvc: KVCache):
+        """x += dense(attention(h)) with h the normed input; appends L rows to ``kvc``."""
+        B, L, _ = h.shape
+        H, G, dh = self.H, self.G, self.dh
+        off = kvc.offset
+        if off + L > self.cos.shape[0]:
+            raise ValueError(f"bailing_moe: position {off + L - 1} is past max_position_embeddings = {self.cos.shape[0]}")
+        slot = kvc.reserve(B, L)
+        q, att = torch.empty(B, L, H * dh, device=h.device), torch.empty(B, L, H * dh, device=h.device)
+        linear(h, self.wq, q)
+        linear(h, self.wkv, slot)
+        ks = slot[:, :, :G * dh]
+        if self.rot == dh:
+            ops.head_norm_rope(q, q, heads=H, dh=dh, norm_weight=self.qn, eps=self.eps, cos=self.cos, sin=self.sin, pos0=off, second=(ks, ks, G, self.kn))
+        else:
+            if self.qn is not None:
+                ops.head_norm_rope(q, q, heads=H, dh=dh, norm_weight=self.qn, eps=self.eps, second=(ks, ks, G, self.kn))
+            ops.partial_rope(q, q, heads=H, dh=dh, rot=self.rot, cos=self.cos, sin=self.sin, pos0=off, second=(ks, ks, G))
+        ops.flash_attention(q, kvc.keys, kvc.values, att, heads=H, kv_heads=G, dh=dh, causal=True)
+        return linear(att, self.dense, x, res=x)
+
+
+class BailingMoeModel:
+    def __init__(self, args: ModelArgs, weights, device="cuda:0", prefix: str = "model."):
+        ops.require_gpu()
+        self.args, self.device = args, torch.device(device)
+        vec = lambda n: weights[prefix + n].to(device=self.device, dtype=torch.float32).contiguous()
+        self.word_embeddings = vec("word_embeddings.weight")
+        self.layers = []
+        for i in range(args.num_hidden_layers):
+            p = f"{prefix}layers.{i}."
+            sparse = args.num_experts is not None and i >= args.first_k_dense_replace
+            mlp = BailingMoeSparseMoeBlock(args, weights, p + "mlp.", self.device) if sparse else BailingMoeMLP(weights, p + "mlp.", self.device)
+            self.layers.append((vec(f"layers.{i}.input_layernorm.weight"), _Attention(args, weights, p + "attention.", self.device),
+                                vec(f"layers.{i}.post_attention_layernorm.weight"), mlp))
+        self.norm = vec("norm.weight")
+
+    def make_cache(self) -> List[KVCache]:
+        a = self.args
+        return [KVCache(a.num_key_value_heads, a.hidden_size // a.num_attention_heads, self.device) for _ in self.layers]
+
+    def __call__(self, inputs: torch.Tensor, cache: Optional[List[KVCache]] = None, trace: Optional[dict] = None) -> torch.Tensor:
+        """inputs [B, L] token ids -> the final-normed hidden states [B, L, D]; ``cache`` (``make_cache``) is extended by L positions."""
+        B, L = inputs.shape
+        eps = self.args.rms_norm_eps
+        cache = self.make_cache() if cache is None else cache
+        x = torch.empty(B, L, self.args.hidden_size, device=self.device)
+        ops.embed_sum(self.word_embeddings, inputs.to(device=self.device, dtype=torch.int32).reshape(B, L, 1), x)
+        h = torch.empty_like(x)
+        for i, ((ln1, attn, ln2, mlp), kvc) in enumerate(zip(self.layers, cache)):
+            attn(ops.rmsnorm(x, h, ln1, eps=eps), x, kvc)
+            ops.rmsnorm(x, h, ln2, eps=eps)
+            if isinstance(mlp, BailingMoeSparseMoeBlock):
+                t = {} if trace is not None else None
+                mlp(h, x, res=x, trace=t)
+                if trace is not None:
+                    trace[f"ids{i}"], trace[f"weights{i}"] = t["ids"], t["weights"]
+            else:
+                mlp(h, x, res=x)
+            if trace is not None:
+                trace[f"layer{i}"] = x.clone()
+        return ops.rmsnorm(x, h, self.norm, eps=eps)
+
+
+class Model:
+    """Token ids -> logits.  ``weights``: a sanitized checkpoint (``sanitize``) under the reference's names."""
+
+    def __init__(self, args: ModelArgs, weights, device="cuda:0"):
+        self.args = args
+        self.model = BailingMoeModel(args, weights, device)
+        head = weights["model.word_embeddings.weight"] if args.tie_word_embeddings else weights["lm_head.weight"]
+        self.lm_head = make_lin(head, None, self.model.device)
+
+    def make_cache(self):
+        return self.model.make_cache()
+
+    def __call__(self, inputs: torch.Tensor, cache=None, trace: Optional[dict] = None) -> torch.Tensor:
+        h = self.model(inputs, cache, trace)
+        return linear(h, self.lm_head, torch.empty(*h.shape[:2], self.args.vocab_size, device=h.device))
+
+
+def make_moe_weights(args: ModelArgs, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A seeded float32 checkpoint under the reference's (sanitized) parameter names."""
+    g = torch.Generator().manual_seed(seed)
+    D, H, G, V = args.hidden_size, args.num_attention_heads, args.num_key_value_heads, args.vocab_size
+    dh = D // H
+    r = lambda *s, fan: torch.randn(*s, generator=g) / fan ** 0.5
+    ln = lambda n: 1.0 + 0.1 * torch.randn(n, generator=g)
+    w = {"model.word_embeddings.weight": torch.randn(V, D, generator=g), "model.norm.weight": ln(D)}
+    if not args.tie_word_embeddings:
+        w["lm_head.weight"] = r(V, D, fan=D)
+    for i in range(args.num_hidden_layers):
+        p = f"model.layers.{i}."
+        w[p + "input_layernorm.weight"], w[p + "post_attention_layernorm.weight"] = ln(D), ln(D)
+        w[p + "attention.query_key_value.weight"], w[p + "attention.dense.weight"] = r((H + 2 * G) * dh, D, fan=D), r(D, H * dh, fan=D)
+        if args.use_qkv_bias:
+            w[p + "attention.query_key_value.bias"] = 0.1 * torch.randn((H + 2 * G) * dh, generator=g)
+        if args.use_bias:
+            w[p + "attention.dense.bias"] = 0.1 * torch.randn(D, generator=g)
+        if args.use_qk_norm:
+            w[p + "attention.query_layernorm.weight"], w[p + "attention.key_layernorm.weight"] = ln(dh), ln(dh)
+        if i >= args.first_k_dense_replace:
+            w.update(_block_weights(args, g, p + "mlp."))
+        else:
+            F = args.intermediate_size
+            for n, shape, fan in (("gate_proj", (F, D), D), ("up_proj", (F, D), D), ("down_proj", (D, F), F)):
+                w[f"{p}mlp.{n}.weight"] = r(*shape, fan=fan)
+                if args.use_bias:
+                    w[f"{p}mlp.{n}.bias"] = 0.1 * torch.randn(shape[0], generator=g)
+    return w
+
+
+def _block_weights(args: ModelArgs, g: torch.Generator, prefix: str) -> Dict[str, torch.Tensor]:
+    D, I, E = args.hidden_size, args.moe_intermediate_size, args.num_experts
+    r = lambda *s, fan: torch.randn(*s, generator=g) / fan ** 0.5
+    w = {f"{prefix}gate.gate_proj.weight": r(E, D, fan=D) * 2.0}
+    for n, shape, fan in (("gate_proj", (E, I, D), D), ("up_proj", (E, I, D), D), ("down_proj", (E, D, I), I)):
+        w[f"{prefix}switch_mlp.{n}.weight"] = r(*shape, fan=fan)
+        if args.use_bias:
+            w[f"{prefix}switch_mlp.{n}.bias"] = 0.1 * torch.randn(E, shape[1], generator=g)
+    if args.moe_router_enable_expert_bias:
+        w[f"{prefix}gate.expert_bias"] = 0.02 * torch.randn(E, generator=g)
+    if args.num_shared_experts > 0 and args.moe_router_enable_shared_expert:
+        S = (args.moe_shared_expert_intermediate_size or I) * args.num_shared_experts
+        for n, shape, fan in (("gate_proj", (S, D), D), ("up_proj", (S, D), D), ("down_proj", (D, S), S)):
+            w[f"{prefix}shared_experts.{n}.weight"] = r(*shape, fan=fan)
+            if args.use_bias:
+                w[f"{prefix}shared_experts.{n}.bias"] = 0.1 * torch.randn(shape[0], generator=g)
+    return w

@@ -2192,3 +2192,141 @@ def qformer_windows(h: torch.Tensor, query: torch.Tensor, positions: torch.Tenso
     _lib.call_struct("mi355_qformer_windows", "mi355_qformer_windows_args", _stream(), h=_ptr(h), h_bstride=hbs, ldh=ldh, lens=_lens_arg(lens, B), B=B, T=T,
                      C=C, block=block, rate=rate, query=_ptr(query), positions=_ptr(positions), queries=_ptr(queries), kv=_ptr(kv))
     return queries, kv
+
+
+# --------------------------------------------------------------------------------------- mixture-of-experts FFN (moe.hip)
+MOE_TILE_ROWS, MOE_COL_TILE, MOE_MAX_EXPERTS, MOE_MAX_TOPK = 32, 64, 512, 16   # MI355_MOE_*
+MOE_SCORE_FN = {"softmax": 0, "sigmoid": 1}
+
+
+@dataclass
+class PackedSwitchLinear:
+    """One ``SwitchLinear``: the bf16 hi + lo image of ``[E, ncols, kdim]`` in B-fragment order (``mi355_moe_pack``) and its float32 bias [E, ncols]."""
+
+    w: torch.Tensor
+    bias: Optional[torch.Tensor]
+    E: int
+    ncols: int
+    kdim: int
+
+
+def pack_switch_linear(w: torch.Tensor, bias: Optional[torch.Tensor], device) -> PackedSwitchLinear:
+    """``w`` float32 [E, out, in] (the reference's ``SwitchLinear.weight``), ``bias`` [E, out] or None.  Packed on the device, once, at load."""
+    assert w.dim() == 3
+    E, ncols, kdim = w.shape
+    lib = _lib.load()
+    wd = w.detach().to(device=device, dtype=torch.float32).contiguous()
+    img = torch.empty(lib.mi355_moe_image_elems(E, ncols, kdim), dtype=torch.int16, device=device)
+    _lib.check(lib.mi355_moe_pack(_ptr(wd), E, ncols, kdim, _ptr(img), _stream()), "mi355_moe_pack")
+    torch.cuda.current_stream().synchronize()   # wd is freed on return
+    bd = None if bias is None else bias.detach().to(device=device, dtype=torch.float32).contiguous()
+    assert bd is None or tuple(bd.shape) == (E, ncols)
+    return PackedSwitchLinear(img, bd, E, ncols, kdim)
+
+
+@dataclass
+class PackedExperts:
+    """The three images of one ``SwitchGLU``: ``gate`` / ``up`` from [E, I, D], ``down`` from [E, D, I]."""
+
+    gate: PackedSwitchLinear
+    up: PackedSwitchLinear
+    down: PackedSwitchLinear
+
+    @classmethod
+    def pack(cls, gate_w, up_w, down_w, device, *, gate_b=None, up_b=None, down_b=None) -> "PackedExperts":
+        E, I, D = gate_w.shape
+        assert tuple(up_w.shape) == (E, I, D) and tuple(down_w.shape) == (E, D, I), (gate_w.shape, up_w.shape, down_w.shape)
+        return cls(pack_switch_linear(gate_w, gate_b, device), pack_switch_linear(up_w, up_b, device), pack_switch_linear(down_w, down_b, device))
+
+    E = property(lambda self: self.gate.E)
+    D = property(lambda self: self.gate.kdim)
+    I = property(lambda self: self.gate.ncols)
+
+
+class MoeWorkspace:
+    """The caller-supplied buffer of ``moe_plan`` / ``switch_glu`` for one (N, k, E, D, I) and typed views of the plan inside it."""
+
+    def __init__(self, N: int, k: int, E: int, D: int, I: int, device, *, nbytes: Optional[int] = None):
+        lay = (ctypes.c_int64 * 8)()
+        _lib.check(_lib.load().mi355_moe_workspace_layout(N, k, E, D, I, ctypes.addressof(lay)), "mi355_moe_workspace_layout")
+        self.dims = (N, k, E, D, I)
+        self.layout = [int(v) for v in lay]
+        self.nbytes = self.layout[6] if nbytes is None else nbytes   # (a short one: the refusal is the library's)
+        self.max_tiles = self.layout[7]
+        self.buf = torch.empty(max(self.nbytes, 16), dtype=torch.uint8, device=device)
+
+    def _i32(self, which: int, n: int) -> torch.Tensor:
+        return self.buf[self.layout[which]:self.layout[which] + 4 * n].view(torch.int32)
+
+    counts = property(lambda self: self._i32(2, self.dims[2]))
+    offsets = property(lambda self: self._i32(3, self.dims[2] + 1))
+    perm = property(lambda self: self._i32(4, self.dims[0] * self.dims[1]))
+    tiles = property(lambda self: self._i32(5, 4 * self.max_tiles).view(self.max_tiles, 4))
+
+
+def moe_route(logits: torch.Tensor, k: int, *, expert_bias: Optional[torch.Tensor] = None, score_function: str = "softmax", n_group: int = 1,
+              topk_group: int = 1, norm_topk_prob: bool = False, routed_scaling_factor: float = 1.0, ids: Optional[torch.Tensor] = None,
+              weights: Optional[torch.Tensor] = None):
+    """``group_expert_select`` of the Ling / Ming router on ``logits`` [N, E] (``mi355_moe_route``) -> ``(ids [N, k] int32, weights [N, k])``: ids in
+    descending selection score, exact ties to the lower index; the weights are the unbiased scores, normalised and scaled."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.float32 and logits.is_cuda
+    N, E = logits.shape
+    ids = torch.empty((N, max(k, 0)), dtype=torch.int32, device=logits.device) if ids is None else ids
+    weights = torch.empty((N, max(k, 0)), dtype=torch.float32, device=logits.device) if weights is None else weights
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and weights.dtype == torch.float32 and weights.is_contiguous()
+    assert tuple(ids.shape) == (N, k) and tuple(weights.shape) == (N, k)
+    assert expert_bias is None or (expert_bias.dtype == torch.float32 and expert_bias.is_contiguous() and expert_bias.numel() == E and expert_bias.is_cuda)
+    _lib.call_struct("mi355_moe_route", "mi355_moe_route_args", _stream(), logits=_ptr(logits), ld=logits.stride(0) if N > 1 else max(logits.stride(0), E),
+                     N=N, E=E, k=k, expert_bias=_ptr(expert_bias), score_fn=MOE_SCORE_FN[score_function], n_group=n_group, topk_group=topk_group,
+                     norm_topk_prob=int(norm_topk_prob), routed_scaling_factor=routed_scaling_factor, ids=_ptr(ids), weights=_ptr(weights))
+    return ids, weights
+
+
+def moe_plan(ids: torch.Tensor, E: int, D: int, I: int, *, ws: Optional[MoeWorkspace] = None) -> MoeWorkspace:
+    """Counting sort of the (token, slot) pairs of ``ids`` [N, k] int32 by expert into ``ws`` (``mi355_moe_plan``): ``ws.counts``, ``ws.offsets``,
+    ``ws.perm`` (stable) and ``ws.tiles`` (expert, first sorted row, rows, 0) -- the plan ``switch_glu`` / ``switch_linear`` run on."""
+    assert ids.dim() == 2 and ids.dtype == torch.int32 and ids.is_contiguous() and ids.is_cuda
+    N, k = ids.shape
+    ws = MoeWorkspace(N, k, E, D, I, ids.device) if ws is None else ws
+    assert ws.dims == (N, k, E, D, I), (ws.dims, (N, k, E, D, I))
+    _lib.call_struct("mi355_moe_plan", "mi355_moe_plan_args", _stream(), ids=_ptr(ids), N=N, k=k, E=E, D=D, I=I, workspace=_ptr(ws.buf),
+                     workspace_bytes=ws.nbytes)
+    return ws
+
+
+def _moe_rows(t: torch.Tensor, N: int, C: int):
+    assert t.dim() == 2 and tuple(t.shape) == (N, C) and t.stride(1) == 1 and t.dtype == torch.float32 and t.is_cuda, (t.shape, t.stride(), t.dtype)
+    return t.stride(0) if N > 1 else max(t.stride(0), C)
+
+
+def switch_glu(x: torch.Tensor, experts: PackedExperts, ids: torch.Tensor, weights: torch.Tensor, out: torch.Tensor, *,
+               shared: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, ws: Optional[MoeWorkspace] = None):
+    """``out[t] = sum_slot weights[t, slot] * SwitchGLU(x[t])[ids[t, slot]] + shared[t] + res[t]`` (``mi355_moe_plan`` + ``mi355_moe_glu``): the
+    routed expert FFN as a grouped GEMM on the matrix pipe, ``silu(gate) * up`` then ``down``, summed in slot order.  ``x`` / ``out`` / ``shared`` /
+    ``res`` [N, D] float32 row views, ``ids`` [N, k] int32, ``weights`` [N, k] float32."""
+    N, D = x.shape
+    k = ids.shape[1]
+    assert ids.shape[0] == N and ids.device == x.device and weights.device == x.device, (ids.shape, x.shape, ids.device, x.device)
+    ws = moe_plan(ids, experts.E, D, experts.I, ws=ws)
+    assert experts.D == D and weights.dtype == torch.float32 and weights.is_contiguous() and tuple(weights.shape) == (N, k) and weights.is_cuda
+    g, u, d = experts.gate, experts.up, experts.down
+    _lib.call_struct("mi355_moe_glu", "mi355_moe_glu_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=experts.E, D=D, I=experts.I,
+                     w_gate=_ptr(g.w), w_up=_ptr(u.w), w_down=_ptr(d.w), b_gate=_ptr(g.bias), b_up=_ptr(u.bias), b_down=_ptr(d.bias),
+                     weights=_ptr(weights), shared=_ptr(shared), ld_shared=0 if shared is None else _moe_rows(shared, N, D), res=_ptr(res),
+                     ld_res=0 if res is None else _moe_rows(res, N, D), out=_ptr(out), ldo=_moe_rows(out, N, D), workspace=_ptr(ws.buf),
+                     workspace_bytes=ws.nbytes, mode=0)
+    return out
+
+
+def switch_linear(x: torch.Tensor, lin: PackedSwitchLinear, ids: torch.Tensor, out: Optional[torch.Tensor] = None, *, ws: Optional[MoeWorkspace] = None):
+    """``out[t, slot] = x[t] @ w[ids[t, slot]]^T + bias[ids[t, slot]]`` -> [N, k, ncols]: one launch of the grouped-GEMM tile kernel on its own
+    (``mi355_moe_glu`` mode 1), the reference's ``SwitchLinear``."""
+    N, D = x.shape
+    k = ids.shape[1]
+    assert lin.kdim == D and ids.shape[0] == N and ids.device == x.device, (ids.shape, x.shape, ids.device, x.device)
+    ws = moe_plan(ids, lin.E, D, lin.ncols, ws=ws)
+    out = torch.empty((N, k, lin.ncols), dtype=torch.float32, device=x.device) if out is None else out
+    assert tuple(out.shape) == (N, k, lin.ncols) and out.dtype == torch.float32 and out.is_cuda and out.stride(2) == 1 and out.stride(0) == k * out.stride(1)
+    _lib.call_struct("mi355_moe_glu", "mi355_moe_glu_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=lin.E, D=D, I=lin.ncols,
+                     w_gate=_ptr(lin.w), b_gate=_ptr(lin.bias), out=_ptr(out), ldo=out.stride(1), workspace=_ptr(ws.buf), workspace_bytes=ws.nbytes, mode=1)
+    return out
