@@ -852,7 +852,10 @@ int mi355_istft(const mi355_istft_args* a, void* stream);
  * q [B, Tq, ldq] with head h at columns [h*dh, (h+1)*dh); k, v [B, Tk, ldk/ldv] with kv head g = h / (heads/kv_heads)
  * at [g*dh, (g+1)*dh) -- a KV cache is simply the buffer k/v point into.  Queries are the LAST lens_q[b] positions of
  * the lens_k[b] keys: key j is visible to query i iff j < lens_k[b], (causal) j <= i + lens_k[b] - lens_q[b],
- * (window > 0) j > i + lens_k[b] - lens_q[b] - window.  softmax(scale * q.k) over the visible keys, times v.
+ * (window > 0) j > i + lens_k[b] - lens_q[b] - window, (k_start) j >= k_start[b].  softmax(scale * q.k) over the visible keys, times v.
+ * A query with no visible key (k_start[b] past its position, causal with lens_q[b] > lens_k[b], lens_k[b] = 0) gets a ZERO row on every
+ * kernel; rows at and past lens_q[b] are not written; cache rows at and past lens_k[b] are not read.  The fused step (new_k) writes cache row
+ * lens_k[b] - 1 and therefore needs lens_k[b] >= 1: an idle slot of a slot cache is carried with lens_k = 1 (position 0), never 0.
  * ------------------------------------------------------------------------------------------ */
 enum { MI355_KV_F32 = 0, MI355_KV_BF16 = 1, MI355_KV_F16 = 2 };
 typedef struct {

@@ -71,7 +71,11 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const mi355_flash_attn_
   const int len_q = a.lens_q ? a.lens_q[b] : a.Tq;
   const int len_k = a.lens_k ? a.lens_k[b] : a.Tk;
   const int q0 = blockIdx.x * 128;
-  if (q0 >= len_q || len_k <= 0) return;
+  if (q0 >= len_q) return;
+  if (len_k <= 0) {  // an item without keys: none of its queries sees one, so its rows are zero (what the decode kernel writes)
+    attn_zero_block<DH>(a.out + (int64_t)b * a.out_bstride + h * DH, a.ldo, q0, len_q, tid);
+    return;
+  }
   const int qoff = len_k - len_q;
   const int qi = q0 + wave * 32 + (lane & 31);
   const bool wave_active = (q0 + wave * 32) < len_q;
@@ -178,7 +182,11 @@ __global__ __launch_bounds__(256) void flash_attn16_kernel(const mi355_flash_att
   const int len_q = a.lens_q ? a.lens_q[b] : a.Tq;
   const int len_k = a.lens_k ? a.lens_k[b] : a.Tk;
   const int q0 = blockIdx.x * 128;
-  if (q0 >= len_q || len_k <= 0) return;
+  if (q0 >= len_q) return;
+  if (len_k <= 0) {  // an item without keys: none of its queries sees one, so its rows are zero (what the decode kernel writes)
+    attn_zero_block<DH>(a.out + (int64_t)b * a.out_bstride + h * DH, a.ldo, q0, len_q, tid);
+    return;
+  }
   const int qoff = len_k - len_q;
   const int qi = q0 + wave * 32 + (lane & 31);
   const bool wave_active = (q0 + wave * 32) < len_q;

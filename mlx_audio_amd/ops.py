@@ -1086,13 +1086,23 @@ def kv_head_major16(kv: torch.Tensor, groups: int, heads: int, dh: int, dtype: t
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, heads: int, kv_heads: Optional[int] = None,
                     dh: int, scale: Optional[float] = None, causal: bool = False, window: int = 0, lens_q=None, lens_k=None,
-                    mode: int = 0, k_start=None, head_major: bool = False, nsplit: int = 0, fused: Optional[dict] = None):
+                    mode: int = 0, k_start=None, head_major: bool = False, nsplit: int = 0, fused: Optional[dict] = None,
+                    out_planes: Optional[torch.Tensor] = None, planes_R: int = 0, planes_f16: bool = False, split_workspace: bool = False):
     """softmax(scale * q k^T + visibility) v.  q/out [B, Tq, >= heads*dh], k/v [B, Tk, >= kv_heads*dh] channels-last views
     (a KV cache is just the buffer k / v point into); see mi355_flash_attn_args for the visibility rule.
     ``fused`` (single-query decode step): dict(new_k, new_v [B, kv_heads * dh] raw projections of the new position, q_norm_w, k_norm_w, eps,
-    cos, sin [rows, dh / 2], rope_mode, pos) -- q / k norms, rotary embedding and the cache store of row Tk - 1 happen inside the attention kernel."""
+    cos, sin [rows, dh / 2], rope_mode, pos) -- q / k norms, rotary embedding and the cache store of row Tk - 1 happen inside the attention kernel.
+    Inside the rows pipeline the dict also carries ``in_kgroups`` / ``in_kg_stride`` (q, new_k and new_v point into slab 0 of that many partial-sum
+    slabs, ``in_kg_stride`` floats apart), ``q_wscale`` / ``k_wscale`` / ``v_wscale`` and ``q_bias`` / ``k_bias`` / ``v_bias`` (per column: sum * scale + bias).
+    ``out_planes`` (int16 / 16-bit tensor of ``2 * planes_R * heads * dh`` elements, ``planes_R`` in 16 / 32 / 64): the single-query output rows also
+    leave as hi + lo planes in bfloat16 (float16 with ``planes_f16``), item b in row b; ``out`` may then be ``None``.
+    ``split_workspace``: hand the key-split workspace over whatever ``nsplit`` says (the library then decides: it splits for ``nsplit >= 2`` only)."""
     B, Tq, _, qbs, ldq = _nlc(q)
-    _, To, _, obs, ldo = _nlc(out)
+    To, obs, ldo = Tq, 0, 0
+    if out is None:
+        assert out_planes is not None, "flash_attention: no destination"
+    else:
+        _, To, _, obs, ldo = _nlc(out)
     khs = vhs = 0
     if head_major:  # k / v [B, kv_heads, Tk, dh]: a head's keys contiguous (the layout for long key ranges: one L2 channel sweep per head)
         assert k.dim() == 4 and v.dim() == 4 and k.stride(3) == 1 and v.stride(3) == 1 and k.shape == v.shape
@@ -1111,9 +1121,15 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torc
         cos, sin = fused.get("cos"), fused.get("sin")
         fkw = dict(new_k=_ptr(nk), new_v=_ptr(nv), new_bstride=nk.stride(0), q_norm_w=_ptr(fused.get("q_norm_w")), k_norm_w=_ptr(fused.get("k_norm_w")),
                    norm_eps=fused.get("eps", 1e-6), rope_cos=_ptr(cos), rope_sin=_ptr(sin), rope_rows=0 if cos is None else cos.shape[0],
-                   rope_mode=fused.get("rope_mode", 0), rope_pos=fused.get("pos", Tk - 1))
+                   rope_mode=fused.get("rope_mode", 0), rope_pos=fused.get("pos", Tk - 1), in_kgroups=fused.get("in_kgroups", 0),
+                   in_kg_stride=fused.get("in_kg_stride", 0), q_bias=_ptr(fused.get("q_bias")), k_bias=_ptr(fused.get("k_bias")),
+                   v_bias=_ptr(fused.get("v_bias")), q_wscale=_ptr(fused.get("q_wscale")), k_wscale=_ptr(fused.get("k_wscale")),
+                   v_wscale=_ptr(fused.get("v_wscale")))
+    if out_planes is not None:
+        assert out_planes.is_cuda and out_planes.is_contiguous() and out_planes.element_size() == 2 and out_planes.numel() >= 2 * planes_R * heads * dh
+        fkw.update(out_planes=_ptr(out_planes), planes_R=planes_R, planes_dtype=1 if planes_f16 else 0)  # MI355_W_F16 / MI355_W_BF16
     sws = scnt = None
-    if nsplit > 1 and Tq <= 8 and mode != 1:
+    if (nsplit > 1 or split_workspace) and Tq <= 8 and mode != 1:
         sws, scnt = attn_split_workspace(q.device, B * heads * Tq, dh)  # key-split decode (flash-decoding), opt-in: measured slower than the unsplit kernel
     _lib.call_struct("mi355_flash_attention", "mi355_flash_attn_args", _stream(), q=_ptr(q), q_bstride=qbs, ldq=ldq, k=_ptr(k),
                      k_bstride=kbs, ldk=ldk, v=_ptr(v), v_bstride=vbs, ldv=ldv, heads=heads, kv_heads=kv_heads or heads, dh=dh,
