@@ -1809,6 +1809,64 @@ typedef struct {
 } mi355_moe_glu_args;
 int mi355_moe_glu(const mi355_moe_glu_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Linear on MLX's affine group-quantised weights (nn.QuantizedLinear / nn.quantize, the `-4bit` / `-8bit` checkpoints; qlinear.hip):
+ *   y[m, n] = epilogue( sum_k x[m, k] * (scale[n, k / g] * q[n, k] + zero[n, k / g]) )
+ * Entry points added to ABI 37 (new structs and functions only).  q: uint32 [N, K bits / 32], element k of a row in word k / (32 / bits) at
+ * bit bits * (k % (32 / bits)), least-significant first (4 bits: the codes 0, 1, ..., 7 pack to 0x76543210).  sz: [N, K / g] (scale, zero)
+ * PAIRS, adjacent, in sz_dtype MI355_KV_F32 (8 bytes a pair) / MI355_KV_BF16 / MI355_KV_F16 (4 bytes a pair): the checkpoint's `.scales` and
+ * `.biases` interleaved, values untouched.  bits 4 or 8, g 32, 64 or 128, K % g == 0 (hence K % 32 == 0); anything else is
+ * MI355_ERR_UNSUPPORTED with the value named, bad pointers / sizes / alignments MI355_ERR_ARG; a refused call launches nothing and leaves
+ * every output untouched.  Per group the kernels form S = sum x_k q_k and X = sum x_k and add fmaf(scale, S, zero * X) in fp32; the codes
+ * never become dequantised floats in memory, and X[m, group] is computed once per workgroup.  Every sum runs in a fixed order: two calls
+ * on the same bytes give the same bits.
+ *   1 .. 8 rows   stream form: 16-byte loads of packed words, codes decoded in registers, fp32 FMAs against x staged in LDS; eight lanes
+ *                 per output column, K split over the four waves of a workgroup (eight columns a workgroup)
+ *   9 rows and up tile form: v_mfma_f32_16x16x32_f16 with the codes as exact fp16 values straight from HBM as the A operand and the input
+ *                 rows split once per workgroup into fp16 hi + lo images in LDS (about 22 mantissa bits of x); a per-group accumulator is
+ *                 folded in the MFMA C layout; 16 columns x 16 or 32 rows a workgroup, K split over its four waves
+ * Epilogue: the one of mi355_gemv (bias, post_act, colscale, res, out_scale, y2 / split / y2_dtype).  norm, glu, rope_cos and x_ids exist
+ * only to be refused by name (MI355_ERR_UNSUPPORTED): fused input norm, GLU, rope and gathered input are not built for this image.
+ * x and q 16-byte aligned, ldx % 4 == 0; y, y2 and res need no alignment.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* x; int32_t ldx; int32_t M; int32_t K; int32_t N;
+  const uint32_t* q; const void* sz; int32_t bits; int32_t group_size; int32_t sz_dtype;
+  const float* bias;       /* [N] nullable */
+  int32_t post_act; float post_slope;
+  const float* colscale;   /* [N] nullable */
+  const float* res; int32_t ldr;
+  float out_scale;         /* 0 => 1 */
+  float* y; int32_t ldy;
+  void* y2; int32_t ldy2; int32_t split; int32_t y2_dtype;   /* columns n >= split go to y2[m, n - split] in MI355_KV_* */
+  int32_t norm; int32_t glu; const float* rope_cos; const int32_t* x_ids;   /* not built: must be 0 / null */
+} mi355_qlinear_args;
+int mi355_qlinear(const mi355_qlinear_args* a, void* stream);
+
+/* What mi355_qlinear would run for `a`, decided without touching the device or dereferencing a pointer of `a`: the same validation (its error
+ * code and text on refusal, *out left alone), then form MI355_QLINEAR_STREAM / MI355_QLINEAR_TILE, the instantiation (bits, group_size, rows =
+ * the rows template of the stream form (1, 2, 4, 8) or the row block of the tile form (16, 32)), the grid, the dynamic LDS bytes and the
+ * input columns staged per chunk. */
+enum { MI355_QLINEAR_STREAM = 1, MI355_QLINEAR_TILE = 2 };
+typedef struct {
+  int32_t form; int32_t bits; int32_t group_size; int32_t rows;
+  int32_t grid_x; int32_t grid_y; int32_t lds_bytes; int32_t chunk_k;
+} mi355_qlinear_route_info;
+int mi355_qlinear_route(const mi355_qlinear_args* a, mi355_qlinear_route_info* out);
+
+/* Floats of the same image, for the paths that need them (an embedding gather; a whole matrix at load for the conv images):
+ *   out[r, k] = (scale * q[row_r, k] + zero) + add[r % add_rows, k]      row_r = rows[r] (device int32, clamped into [0, N)) or r when rows is null
+ * The product and the sums are rounded one at a time in float32, in that order (no fused multiply-add): bit-equal to
+ * float32(scale) * q + float32(zero) evaluated elementwise.  add nullable (the positional rows of a token gather).  out 16-byte aligned,
+ * ldo % 4 == 0 (and ld_add % 4 == 0); same format rules and refusals as mi355_qlinear. */
+typedef struct {
+  const uint32_t* q; const void* sz; int32_t bits; int32_t group_size; int32_t sz_dtype; int32_t N; int32_t K;
+  const int32_t* rows; int32_t n_rows;
+  const float* add; int32_t ld_add; int32_t add_rows;
+  float* out; int32_t ldo;
+} mi355_dequantize_affine_args;
+int mi355_dequantize_affine(const mi355_dequantize_affine_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2346,3 +2346,141 @@ def switch_linear(x: torch.Tensor, lin: PackedSwitchLinear, ids: torch.Tensor, o
     _lib.call_struct("mi355_moe_glu", "mi355_moe_glu_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=lin.E, D=D, I=lin.ncols,
                      w_gate=_ptr(lin.w), b_gate=_ptr(lin.bias), out=_ptr(out), ldo=out.stride(1), workspace=_ptr(ws.buf), workspace_bytes=ws.nbytes, mode=1)
     return out
+
+
+# --------------------------------------------------------------------------------------- MLX affine group quantisation (qlinear.hip)
+QLINEAR_STREAM, QLINEAR_TILE = 1, 2   # mi355_qlinear_route_info.form
+
+
+@dataclass
+class QuantizedLinear:
+    """One ``nn.QuantizedLinear`` / ``nn.QuantizedEmbedding`` of a `-4bit` / `-8bit` MLX checkpoint on the device: the packed words as they are in the
+    file and the checkpoint's ``.scales`` / ``.biases`` interleaved into adjacent (scale, zero) pairs, values untouched."""
+
+    q: torch.Tensor    # int32 [N, K * bits / 32]: element k of a row in word k / (32 / bits) at bit bits * (k % (32 / bits))
+    sz: torch.Tensor   # [N, K / group_size, 2] in the checkpoint's 16-bit type or float32
+    bias: Optional[torch.Tensor]
+    n: int
+    k: int
+    bits: int
+    group_size: int
+
+
+def _words(w: torch.Tensor) -> torch.Tensor:
+    assert w.dim() == 2 and w.dtype in (torch.uint32, torch.int32), (w.shape, w.dtype)
+    return w.contiguous().view(torch.int32)
+
+
+def infer_quantization(words_per_row: int, groups_per_row: int, *, group_size: Optional[int] = None, bits: Optional[int] = None) -> Tuple[int, int]:
+    """(bits, group_size) of a packed ``.weight`` [N, words] beside ``.scales`` [N, groups].  The shapes fix the product bits * group_size =
+    32 * words / groups; where that leaves two readings (256: 4 x 64 or 8 x 32; 512: 4 x 128 or 8 x 64) MLX's default group of 64 is taken unless
+    ``group_size`` or ``bits`` (the checkpoint's ``quantization`` config) says otherwise."""
+    assert groups_per_row > 0 and (32 * words_per_row) % groups_per_row == 0, (words_per_row, groups_per_row)
+    prod = 32 * words_per_row // groups_per_row
+    if group_size is None:
+        group_size = prod // bits if bits is not None else (64 if prod in (256, 512) else (32 if prod == 128 else 128))
+    if bits is None:
+        bits = prod // group_size
+    if bits * group_size != prod:
+        raise ValueError(f"bits = {bits} and group_size = {group_size} do not match a [N, {words_per_row}] weight with [N, {groups_per_row}] scales")
+    return bits, group_size
+
+
+def pack_quantized(weight_u32: torch.Tensor, scales: torch.Tensor, biases: torch.Tensor, bias: Optional[torch.Tensor], device, *,
+                   group_size: Optional[int] = None, bits: Optional[int] = None) -> QuantizedLinear:
+    """The device image of one quantised parameter: ``weight_u32`` uint32 [N, K bits / 32], ``scales`` / ``biases`` [N, K / g] (MLX's affine mode),
+    ``bias`` the Linear's own [N] or None.  ``bits`` / ``group_size`` are inferred from the shapes when not given (``infer_quantization``)."""
+    q = _words(weight_u32)
+    assert scales.shape == biases.shape and scales.dim() == 2 and scales.shape[0] == q.shape[0], (q.shape, scales.shape, biases.shape)
+    bits, group_size = infer_quantization(q.shape[1], scales.shape[1], group_size=group_size, bits=bits)
+    dt = scales.dtype if scales.dtype in (torch.float16, torch.bfloat16) else torch.float32
+    sz = torch.stack([scales.to(dt), biases.to(dt)], dim=-1).contiguous()
+    bd = None if bias is None else bias.detach().to(torch.float32).contiguous().to(device)
+    return QuantizedLinear(q.to(device), sz.to(device), bd, q.shape[0], scales.shape[1] * group_size, bits, group_size)
+
+
+def _rows2d(t: torch.Tensor, cols: int) -> int:
+    assert t.dim() == 2 and t.shape[1] == cols and t.stride(1) == 1, (t.shape, t.stride(), cols)
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), cols)
+
+
+def qlinear(x: torch.Tensor, ql: QuantizedLinear, y: torch.Tensor, *, post_act: int = ACT_NONE, post_slope: float = 0.0,
+            res: Optional[torch.Tensor] = None, colscale: Optional[torch.Tensor] = None, out_scale: float = 1.0, y2: Optional[torch.Tensor] = None,
+            use_bias: bool = True):
+    """y[m, :] = epilogue(x[m, :] @ dequantised(W)^T) on the packed codes (``mi355_qlinear``): 1..8 rows the stream form, 9 and up the tile form.
+    x / y / res are 2-D fp32 views with unit inner stride and any row stride; ``y2``: columns >= y.shape[1] go there (a KV-cache slot, fp32 or 16-bit)."""
+    assert x.dtype == torch.float32 and y.dtype == torch.float32 and x.is_cuda
+    M = x.shape[0]
+    n_y = ql.n if y2 is None else ql.n - y2.shape[1]
+    assert y.shape[0] == M, (x.shape, y.shape)
+    kw = dict(x=_ptr(x), ldx=_rows2d(x, ql.k), M=M, K=ql.k, N=ql.n, q=_ptr(ql.q), sz=_ptr(ql.sz), bits=ql.bits, group_size=ql.group_size,
+              sz_dtype=KV_DTYPES[ql.sz.dtype], bias=_ptr(ql.bias) if use_bias else None, post_act=post_act, post_slope=post_slope,
+              colscale=_ptr(colscale), out_scale=out_scale, y=_ptr(y), ldy=_rows2d(y, n_y))
+    if res is not None:
+        assert res.dtype == torch.float32 and res.shape[0] == M
+        kw.update(res=_ptr(res), ldr=_rows2d(res, ql.n))
+    if y2 is not None:
+        assert y2.shape[0] == M and y2.dtype in KV_DTYPES
+        kw.update(y2=_ptr(y2), ldy2=_rows2d(y2, ql.n - n_y), split=n_y, y2_dtype=KV_DTYPES[y2.dtype])
+    _lib.call_struct("mi355_qlinear", "mi355_qlinear_args", _stream(), **kw)
+    return y
+
+
+def qlinear_route(M: int, N: int, K: int, bits: int, group_size: int, *, sz_dtype: torch.dtype = torch.float16, **fields) -> dict:
+    """What ``qlinear`` would run for these sizes (``mi355_qlinear_route``: form, bits, group_size, rows, grid_x, grid_y, lds_bytes, chunk_k), or its
+    refusal as ``Mi355Error``.  Needs no device: the addresses are made up (aligned, non-null) and never read.  ``fields`` overrides any struct field."""
+    kw = dict(x=0x10000000, ldx=K, M=M, K=K, N=N, q=0x20000000, sz=0x30000000, bits=bits, group_size=group_size, sz_dtype=KV_DTYPES[sz_dtype],
+              y=0x40000000, ldy=N)
+    kw.update(fields)
+    return _lib.call_struct_out("mi355_qlinear_route", "mi355_qlinear_args", "mi355_qlinear_route_info", **kw)
+
+
+def dequantize_affine(ql: QuantizedLinear, rows: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
+                      add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Floats of a quantised parameter (``mi355_dequantize_affine``): the whole matrix [N, K], or the rows ``rows`` (int32, device) of the table --
+    an embedding gather.  Every element is float32(scale) * q + float32(zero) with the product and the sum rounded separately, bit-equal to that
+    expression in torch.  ``add`` [P, K]: row r also receives ``add[r % P]`` (the positional rows of a token block)."""
+    if rows is not None:
+        rows = rows.reshape(-1).contiguous()
+        assert rows.dtype == torch.int32 and rows.is_cuda
+    n_rows = ql.n if rows is None else rows.numel()
+    out = torch.empty((n_rows, ql.k), dtype=torch.float32, device=ql.q.device) if out is None else out
+    assert out.dtype == torch.float32 and out.shape[0] == n_rows
+    kw = dict(q=_ptr(ql.q), sz=_ptr(ql.sz), bits=ql.bits, group_size=ql.group_size, sz_dtype=KV_DTYPES[ql.sz.dtype], N=ql.n, K=ql.k, rows=_ptr(rows),
+              n_rows=n_rows, out=_ptr(out), ldo=_rows2d(out, ql.k))
+    if add is not None:
+        assert add.dtype == torch.float32
+        kw.update(add=_ptr(add), ld_add=_rows2d(add, ql.k), add_rows=add.shape[0])
+    _lib.call_struct("mi355_dequantize_affine", "mi355_dequantize_affine_args", _stream(), **kw)
+    return out
+
+
+def unpack_codes(weight_u32: torch.Tensor, bits: int) -> torch.Tensor:
+    """uint32 [N, K bits / 32] -> the integer codes [N, K] (int64), in plain torch."""
+    w = _words(weight_u32).to(torch.int64) & 0xFFFFFFFF
+    shifts = torch.arange(0, 32, bits, dtype=torch.int64, device=w.device)
+    return ((w[:, :, None] >> shifts) & ((1 << bits) - 1)).reshape(w.shape[0], -1)
+
+
+def pack_codes(codes: torch.Tensor, bits: int) -> torch.Tensor:
+    """Integer codes [N, K] -> MLX's packed uint32 [N, K bits / 32]: element k in word k / (32 / bits) at bit bits * (k % (32 / bits))."""
+    epw = 32 // bits
+    assert codes.dim() == 2 and codes.shape[1] % epw == 0 and int(codes.min()) >= 0 and int(codes.max()) < (1 << bits)
+    shifts = torch.arange(0, 32, bits, dtype=torch.int64, device=codes.device)
+    v = (codes.to(torch.int64).reshape(codes.shape[0], -1, epw) << shifts).sum(-1)
+    return (v - ((v >> 31) << 32)).to(torch.int32).view(torch.uint32)
+
+
+def quantize_affine(w: torch.Tensor, group_size: int = 64, bits: int = 4) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """MLX's affine group quantisation in plain torch, for producing checkpoints: ``(weight uint32 [N, K bits / 32], scales, biases [N, K / g])`` in
+    ``w``'s floating type.  Per group: scale = (max - min) / (2^bits - 1), zero = min, code = round((w - zero) / scale) clipped to the code range;
+    a constant group (max == min) takes MLX's floor of 1e-7 for the scale, so its codes are 0 and its value sits in the zero.  Computed in float32;
+    scale and zero are rounded to the output type BEFORE the codes are taken, so a 16-bit checkpoint dequantises to within half a step of ``w``."""
+    assert w.dim() == 2 and w.shape[1] % group_size == 0 and bits in (2, 4, 8) and w.is_floating_point()   # the widths that fill a word
+    n, k = w.shape
+    g = w.detach().to(torch.float32).reshape(n, k // group_size, group_size)
+    lo, hi = g.amin(-1), g.amax(-1)
+    scale = ((hi - lo) / float((1 << bits) - 1)).clamp_min(1e-7).to(w.dtype)
+    zero = lo.to(w.dtype)
+    codes = torch.round((g - zero.float()[..., None]) / scale.float()[..., None]).clamp_(0, (1 << bits) - 1).to(torch.int64)
+    return pack_codes(codes.reshape(n, k), bits), scale, zero

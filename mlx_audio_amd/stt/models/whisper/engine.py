@@ -13,7 +13,13 @@ reference's op-by-op graph collapsed into:
     for decode steps) reading K / V straight out of the caches the projection GEMMs wrote into;
   * decode steps (1 row per sequence) switch every Linear to the HBM-bound ``mi355_gemv`` on the row-major fp16 image, and
     the whole filter + arg-max + log-prob bookkeeping of a step is one kernel -- the loop runs without host round trips
-    (completion is polled every ``poll`` steps; results do not depend on when the loop stops).
+    (completion is polled every ``poll`` steps; results do not depend on when the loop stops);
+  * a quantised checkpoint (MLX `-4bit` / `-8bit`: ``quantized``) keeps its DECODER linears packed: self-attention q | k | v (packed rows
+    concatenated), the cross query, both ``out`` projections, ``mlp1``, ``mlp2`` and the tied logits run on ``ops.qlinear`` at every row count, the
+    pre-LayerNorm as its own launch, and the token gather dequantises the rows it reads.  Such an engine does not use the native runner or the
+    rows-pipeline logits (neither knows this image).  Quantised ENCODER linears and the cross ``key`` / ``value`` projections (1500 rows per window:
+    bound by the matrix pipe, not by the weight stream) are dequantised once at load into the usual fp16 images, so their dequantised values
+    are ROUNDED TO FP16 there; the decoder's packed linears use scale * q + zero unrounded.
 
 Everything here is plumbing (allocation, views, launch order); all arithmetic on activations is in libmi355audio.so.
 """
@@ -37,6 +43,7 @@ from .synthetic import ModelDimensions
 class _Lin:
     pc: PackedConv      # MFMA fragment order (prefill / encoder)
     rm: RowMajor16      # row-major fp16 (decode-step GEMV)
+    ql: Optional[ops.QuantizedLinear] = None   # packed MLX codes (a quantised decoder Linear: every row count; pc and rm are then None)
 
 
 @dataclass
@@ -71,7 +78,10 @@ def sinusoids(length: int, channels: int, max_timescale: float = 10000) -> torch
 
 class WhisperEngine:
     def __init__(self, weights: Dict[str, torch.Tensor], dims: ModelDimensions, device: str = "cuda:0", precision: int = 4,
-                 kv_dtype: torch.dtype = torch.float16, pos_dtype: torch.dtype = torch.float16):
+                 kv_dtype: torch.dtype = torch.float16, pos_dtype: torch.dtype = torch.float16, quantized: Optional[Dict[str, tuple]] = None,
+                 quantization: Optional[dict] = None):
+        """``quantized``: {parameter prefix: (weight uint32, scales, biases)} of the quantised Linears / Embedding of an MLX checkpoint (``weights`` then
+        holds only their ``.bias``); ``quantization``: optional {"group_size", "bits"} where the shapes alone leave two readings (``ops.infer_quantization``)."""
         ops.require_gpu()
         assert precision in (3, 4)
         assert kv_dtype in ops.KV_DTYPES
@@ -94,31 +104,51 @@ class WhisperEngine:
         self.dh = dims.n_audio_state // dims.n_audio_head
         assert self.dh in (64, 128) and dims.n_text_state // dims.n_text_head == self.dh
         assert max(dims.n_audio_state, dims.n_text_state) <= 1024, "layernorm kernel holds <= 1024 channels per row"
-        w = {k: v.detach().to(torch.float16).to(torch.float32).cpu() for k, v in weights.items()}  # checkpoint dtype: fp16
         dev = self.device
+        quantized = dict(quantized or {})
+        qcfg = {k: v for k, v in (quantization or {}).items() if k in ("group_size", "bits")}
+        qfmt = {p: ops.infer_quantization(t[0].shape[1], t[1].shape[1], **qcfg) for p, t in quantized.items()}
+        # the parameters that stay packed: decoder linears off the 1500-row products; q | k | v only as a whole, in one format
+        packed = {p for p in quantized if p == "decoder.token_embedding" or (p.startswith("decoder.blocks.") and p.rsplit(".", 1)[1] in ("out", "mlp1", "mlp2"))
+                  or p.endswith(".cross_attn.query")}
+        for i in range(dims.n_text_layer):
+            qkv = [f"decoder.blocks.{i}.attn.{a}" for a in ("query", "key", "value")]
+            if all(p in quantized for p in qkv) and len({qfmt[p] for p in qkv}) == 1:
+                packed.update(qkv)
+        weights = dict(weights)
+        for p in quantized.keys() - packed:   # dequantised once, here; rounded to fp16 with every other weight below
+            weights[p + ".weight"] = ops.dequantize_affine(ops.pack_quantized(*quantized[p], None, dev, **qcfg)).cpu()
+        self.quantized_decoder = bool(packed)
+        w = {k: v.detach().to(torch.float16).to(torch.float32).cpu() for k, v in weights.items()}  # checkpoint dtype: fp16
 
-        def lin(wt, bias):
+        def lin(names, bias):
+            """One Linear over the concatenated rows of the parameters ``names``."""
+            names = [names] if isinstance(names, str) else names
+            if names[0] in packed:
+                q, s, b = (torch.cat([quantized[p][j].view(torch.int32) if j == 0 else quantized[p][j] for p in names]) for j in range(3))
+                return _Lin(None, None, ops.pack_quantized(q, s, b, bias, dev, **qcfg))
+            wt = torch.cat([w[p + ".weight"] for p in names])
             return _Lin(ops.pack_conv(wt, bias, dev, f16=True), ops.pack_rowmajor16(wt, bias, dev, f16=True))
 
         def ln(name):
             return _LN(w[name + ".weight"].to(dev), w[name + ".bias"].to(dev))
 
         def block(pfx, n, cross):
-            def att(a):
-                wq, bq = w[f"{pfx}.{a}.query.weight"], w[f"{pfx}.{a}.query.bias"]
-                wk = w[f"{pfx}.{a}.key.weight"]
-                wv, bv = w[f"{pfx}.{a}.value.weight"], w[f"{pfx}.{a}.value.bias"]
-                z = torch.zeros(n)
-                return (lin(torch.cat([wq, wk, wv]), torch.cat([bq, z, bv])), lin(wq, bq), lin(torch.cat([wk, wv]), torch.cat([z, bv])),
-                        lin(w[f"{pfx}.{a}.out.weight"], w[f"{pfx}.{a}.out.bias"]))
+            def att(a, fused):
+                names = [f"{pfx}.{a}.{t}" for t in ("query", "key", "value")]
+                bq, bv, z = w[names[0] + ".bias"], w[names[2] + ".bias"], torch.zeros(n)   # the key projection has no bias: zero entries
+                qkv = lin(names, torch.cat([bq, z, bv])) if fused else None
+                sep = fused and qkv.ql is not None   # a packed q | k | v serves every row count: no separate q and k | v images
+                return (qkv, None if sep else lin(names[:1], bq), None if sep else lin(names[1:], torch.cat([z, bv])),
+                        lin(f"{pfx}.{a}.out", w[f"{pfx}.{a}.out.bias"]))
 
-            qkv, q, kv, out = att("attn")
+            qkv, q, kv, out = att("attn", True)
             cq = ckv = cout = cln = None
             if cross:
-                _, cq, ckv, cout = att("cross_attn")
+                _, cq, ckv, cout = att("cross_attn", False)
                 cln = ln(f"{pfx}.cross_attn_ln")
             return _Block(ln(f"{pfx}.attn_ln"), qkv, q, kv, out, cln, cq, ckv, cout, ln(f"{pfx}.mlp_ln"),
-                          lin(w[f"{pfx}.mlp1.weight"], w[f"{pfx}.mlp1.bias"]), lin(w[f"{pfx}.mlp2.weight"], w[f"{pfx}.mlp2.bias"]))
+                          lin(f"{pfx}.mlp1", w[f"{pfx}.mlp1.bias"]), lin(f"{pfx}.mlp2", w[f"{pfx}.mlp2.bias"]))
 
         na = dims.n_audio_state
         self.conv1 = ops.pack_conv(w["encoder.conv1.weight"], w["encoder.conv1.bias"], dev, f16=True)
@@ -136,11 +166,13 @@ class WhisperEngine:
         self.enc_pos = sinusoids(dims.n_audio_ctx, na).to(pos_dtype).to(torch.float32).to(dev)[None]
         self.enc_blocks = [block(f"encoder.blocks.{i}", na, False) for i in range(dims.n_audio_layer)]
         self.ln_post = ln("encoder.ln_post")
-        self.tok_emb = w["decoder.token_embedding.weight"].to(dev)
+        self.logits_lin = lin("decoder.token_embedding", None)  # tied: token_embedding.as_linear (whisper.py:498)
+        self.tok_emb = w["decoder.token_embedding.weight"].to(dev) if self.logits_lin.ql is None else None   # packed: the gather dequantises its rows
         self.pos_emb = w["decoder.positional_embedding"].to(dev)
         self.dec_blocks = [block(f"decoder.blocks.{i}", dims.n_text_state, True) for i in range(dims.n_text_layer)]
         self.ln = ln("decoder.ln")
-        self.logits_lin = lin(w["decoder.token_embedding.weight"], None)  # tied: token_embedding.as_linear (whisper.py:498)
+        if self.quantized_decoder:
+            self.native_decode = False   # stack_step.cpp knows nothing of the packed image
 
     # ------------------------------------------------------------------ helpers
     def _f(self, *shape):
@@ -152,7 +184,12 @@ class WhisperEngine:
         kernels, 9..64 rows: gemm_rows.hip), which also fuses the pre-LayerNorm (``ln``) and can split its columns over two destinations
         (``y2``: q -> y, k | v -> the KV-cache slot)."""
         B, L, _ = x.shape
-        if L == 1 and B <= 64:
+        if l.ql is not None:   # packed codes: one kernel family for every row count, the pre-LayerNorm as its own launch
+            if ln is not None:
+                x = self._lnorm(x, ln)
+            ops.qlinear(x.flatten(0, 1), l.ql, y.view(B * L, y.shape[2]), post_act=post_act, res=None if res is None else res.view(B * L, res.shape[2]),
+                        y2=None if y2 is None else y2[:, 0, :])
+        elif L == 1 and B <= 64:
             ops.gemv(x[:, 0, :], l.rm, y[:, 0, :], post_act=post_act, res=None if res is None else res[:, 0, :],
                      norm=None if ln is None else ("layer", ln.w, ln.b, 1e-5), y2=None if y2 is None else y2[:, 0, :])
         else:
@@ -305,7 +342,10 @@ class WhisperEngine:
         assert off + n <= d.n_text_ctx
         nt, H, dh = d.n_text_state, d.n_text_head, self.dh
         x = self._f(B, n, nt)
-        ops.gather_rows(self.tok_emb, tokens, x, pos_table=self.pos_emb[off:off + n])
+        if self.tok_emb is None:   # packed table: the rows the tokens name, dequantised, plus the positional rows
+            ops.dequantize_affine(self.logits_lin.ql, tokens, out=x.view(B * n, nt), add=self.pos_emb[off:off + n])
+        else:
+            ops.gather_rows(self.tok_emb, tokens, x, pos_table=self.pos_emb[off:off + n])
         if n == 1 and B <= 64 and self.native_decode and cross_hook is None:  # the whole 12-layer step from the native runner: one call instead of ~100 launches from Python
             nd = self._native_desc(st)
             ws = self._f(B * (2 * nt + 4 * nt + 2 * nt))
@@ -319,13 +359,18 @@ class WhisperEngine:
         mid = self._f(B, n, 4 * nt)
         for i, blk in enumerate(self.dec_blocks):
             cache = st["self_kv"][i]
-            if n == 1 and B <= 64:  # decode step: LayerNorm + q | k | v in one GEMV, k | v written straight into the cache slot
+            qv = q
+            if n == 1 and (B <= 64 or blk.qkv.ql is not None):  # decode step: LayerNorm + q | k | v in one GEMV, k | v written straight into the cache slot
                 self._linear(x, blk.qkv, q, ln=blk.attn_ln, y2=cache[:, off:off + 1, :])
+            elif blk.qkv.ql is not None:   # prompt rows on the packed q | k | v: the rows of B windows' cache slots are not one 2-D view, so k | v pass through a block
+                qkv = self._linear(x, blk.qkv, self._f(B, n, 3 * nt), ln=blk.attn_ln)
+                cache[:, off:off + n, :].copy_(qkv[:, :, nt:])
+                qv = qkv[:, :, :nt]
             else:
                 h = self._lnorm(x, blk.attn_ln)
                 self._linear(h, blk.q, q)
                 self._linear(h, blk.kv, cache[:, off:off + n, :])
-            ops.flash_attention(q, cache[:, :off + n, 0:nt], cache[:, :off + n, nt:], att, heads=H, dh=dh, scale=dh ** -0.5, causal=True)
+            ops.flash_attention(qv, cache[:, :off + n, 0:nt], cache[:, :off + n, nt:], att, heads=H, dh=dh, scale=dh ** -0.5, causal=True)
             self._linear(att, blk.out, x, res=x)
             self._linear(x, blk.cq, q, ln=blk.cross_ln)
             if cross_hook is not None:
@@ -342,7 +387,7 @@ class WhisperEngine:
         B, n, _ = hidden.shape
         vp = ops.round_up(self.dims.n_vocab, 4)
         out = self._f(B, n, vp)
-        if n == 1 and self.rows_min <= B <= 64 and os.environ.get("MI355_WHISPER_LOGITS_ROWS", "1") != "0":
+        if n == 1 and self.rows_min <= B <= 64 and self.logits_lin.ql is None and os.environ.get("MI355_WHISPER_LOGITS_ROWS", "1") != "0":
             # decode step of a tall batch: the 51 865 x 768 tied head on the rows pipeline (tile image x pre-split planes, ONE K group: the slab a
             # workgroup writes IS the logits -- no bias, no epilogue launch).  The one-launch gemm_rows kernel re-reads and re-splits all B rows in each of its
             # 3 242 workgroups: 86 us per step at 64 windows against ~30 us here (profiles/r6_kernel_stats_whisper_b64_call16.txt).  MI355_WHISPER_LOGITS_ROWS=0: A/B knob

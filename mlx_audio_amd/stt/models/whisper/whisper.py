@@ -18,6 +18,7 @@ has no host implementation, so a ``Model`` without an engine raises ``NotImpleme
 Deliberately not carried over (host front/back ends): resampling of non-16 kHz files and streaming (AlignAtt), which raises
 ``NotImplementedError``.
 ``detect_language`` returns the reference's (language tokens, probability dicts) pair.
+Quantised checkpoints (MLX affine `-4bit` / `-8bit`, whisper.py:671-688) load: see ``load_weights``.  Other quantisation modes are not built.
 """
 from __future__ import annotations
 
@@ -160,11 +161,19 @@ class Model:
             out[k] = v
         return out
 
-    def load_weights(self, weights, strict: bool = True):
+    def load_weights(self, weights, strict: bool = True, quantization: Optional[dict] = None):
+        """A parameter ``name`` is quantised (MLX affine mode, the `-4bit` / `-8bit` checkpoints) when ``name.scales`` is among the weights -- the
+        reference's predicate (whisper.py:671-688), Linear and Embedding alike and per parameter, so partly quantised checkpoints load.  Bits and
+        group size follow from the shapes (``ops.infer_quantization``; ``quantization`` = the checkpoint's {"group_size", "bits"} where given).  The
+        decoder's linears then run on the packed codes (``ops.qlinear``); the encoder's and the cross key / value projections are dequantised
+        once, here, and rounded to fp16 into the usual images (engine.py).  A checkpoint without ``.scales`` takes exactly the float path."""
         from .engine import WhisperEngine
 
         w = dict(weights)
+        quantized = {k[:-7]: None for k in w if k.endswith(".scales")}
         try:
+            for p in quantized:
+                quantized[p] = (w.pop(p + ".weight"), w.pop(p + ".scales"), w.pop(p + ".biases"))
             # the K / V caches live in the checkpoint's floating dtype like the reference's (whisper.py:360-361): fp16 -> fp16, bf16 -> bf16, fp32 -> fp32
             fdt = [v.dtype for v in w.values() if v.is_floating_point()]
             kv_dtype = max(set(fdt), key=fdt.count) if fdt else torch.float16
@@ -172,7 +181,8 @@ class Model:
             if kv_dtype not in (torch.float16, torch.bfloat16, torch.float32):
                 kv_dtype = torch.float32
             self.engine = WhisperEngine({k: v.to(torch.float32) for k, v in w.items() if v.is_floating_point()}, self.dims,
-                                        device=self.device, precision=self.precision, kv_dtype=kv_dtype, pos_dtype=kv_dtype)
+                                        device=self.device, precision=self.precision, kv_dtype=kv_dtype, pos_dtype=kv_dtype, quantized=quantized,
+                                        quantization=quantization)
         except KeyError as e:
             raise ValueError(f"Whisper checkpoint is missing parameter {e}") from e
         return self
