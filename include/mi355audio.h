@@ -1809,6 +1809,41 @@ typedef struct {
 } mi355_moe_glu_args;
 int mi355_moe_glu(const mi355_moe_glu_args* a, void* stream);
 
+/* SwitchGLU on MLX's affine group-quantised expert weights (QuantizedSwitchLinear of the `-4bit` / `-8bit` Ling / Ming checkpoints;
+ * moe_quant.hip).  Added to ABI 37 (a new struct and a new function only).  It runs behind the same mi355_moe_plan, workspace, tile list and
+ * combine as mi355_moe_glu; only the two tile launches differ: their weight operand is the packed codes as they are in the checkpoint.
+ * Per projection: q uint32 [E, Ncols, Kdim bits / 32] (element k of a row in word k / (32 / bits) at bit bits * (k % (32 / bits))), sz the
+ * (scale, zero) PAIRS [E, Ncols, Kdim / g] in sz_dtype MI355_KV_F32 / MI355_KV_BF16 / MI355_KV_F16 (`.scales` and `.biases` interleaved, values
+ * untouched), a float32 bias [E, Ncols] (nullable).  Per tile (at most MI355_MOE_TILE_ROWS sorted rows r of one expert e):
+ *   out[r, n] = sum over groups of fmaf(scale[e, n, group], S, zero[e, n, group] * X[r, group]) + bias[e, n]
+ *   S = sum over the group of x[r, k] * q[e, n, k],  X = sum over the group of x[r, k]
+ * in fp32 and a fixed order: the arithmetic of mi355_qlinear's tile form.  The codes go from HBM into registers and become exact fp16 A
+ * operands of v_mfma_f32_16x16x32_f16 (no dequantised float in memory, no LDS hop); the tile's rows are gathered through perm, split once per
+ * workgroup into fp16 hi + lo images (about 22 mantissa bits of x; |x| above 65504 saturates, |x| below 2^-24 is dropped: the limits of
+ * mi355_qlinear's tile form) and staged in LDS, 256 K values at a time; two products per step (x hi, x lo).  A workgroup is 32 output columns of
+ * one tile: wave (c, p) owns columns [16 c, 16 c + 16) and the groups p, p + 2, ... of K; the two K parts are joined through LDS, part 0 +
+ * part 1.  The grid is max_tiles x ceil(columns / MI355_MOE_QCOL_TILE); a tile of one row and a tile of 32 rows run the same kernel.
+ * mode 0, three launches: h = silu(gate + b_gate) * (up + b_up) in sorted order (the gate and up streams share one staged x and one X);
+ * y = h @ down + b_down scattered through perm; the combine of mi355_moe_glu.  mode 1, one launch: out[t k + slot] = x[t] @ gate[e]^T +
+ * b_gate[e] with the gate image as [E, Ncols = I, Kdim = D] (a plain QuantizedSwitchLinear); up, down, weights, shared and res are ignored.
+ * bits 4 or 8, group_size 32, 64 or 128, gate and up in ONE format (down may differ), else MI355_ERR_UNSUPPORTED with the value named;
+ * null pointers, q not 16-byte aligned, pairs not aligned to their size, Kdim % group_size != 0, the row rules of mi355_moe_glu or a short
+ * workspace are MI355_ERR_ARG.  A refused call launches nothing.  No floating-point atomics, no persistent loops; a token's output does not
+ * depend on which other tokens share the call, and two calls on the same bytes give the same bits. */
+#define MI355_MOE_QCOL_TILE 32    /* output columns of one workgroup of the quantised tile kernel: two waves of 16 columns, times two K parts */
+typedef struct {
+  const float* x; int64_t ldx; int32_t N; int32_t k; int32_t E; int32_t D; int32_t I;
+  const uint32_t* q_gate; const void* sz_gate; int32_t bits_gate; int32_t group_gate; int32_t szdt_gate;
+  const uint32_t* q_up; const void* sz_up; int32_t bits_up; int32_t group_up; int32_t szdt_up;
+  const uint32_t* q_down; const void* sz_down; int32_t bits_down; int32_t group_down; int32_t szdt_down;
+  const float* b_gate; const float* b_up; const float* b_down;
+  const float* weights;
+  const float* shared; int64_t ld_shared; const float* res; int64_t ld_res;
+  float* out; int64_t ldo;
+  void* workspace; int64_t workspace_bytes; int32_t mode;
+} mi355_moe_qglu_args;
+int mi355_moe_qglu(const mi355_moe_qglu_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Linear on MLX's affine group-quantised weights (nn.QuantizedLinear / nn.quantize, the `-4bit` / `-8bit` checkpoints; qlinear.hip):
  *   y[m, n] = epilogue( sum_k x[m, k] * (scale[n, k / g] * q[n, k] + zero[n, k / g]) )

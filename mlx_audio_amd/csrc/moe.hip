@@ -14,7 +14,7 @@
 // staged.  The K groups are joined through LDS in a fixed order.  Three MFMAs per fragment pair (hi.hi, hi.lo, lo.hi) give float32-level
 // products: what is dropped is lo.lo and the residual of the two splits, each below 2^-16 of |x| |w|.
 #include <limits.h>
-#include "common.h"
+#include "moe_common.h"
 
 namespace {
 
@@ -23,25 +23,6 @@ constexpr int KC = 128;               // K values staged per chunk
 constexpr int KSTEPS = KC / 16;       // MFMA K steps per chunk
 constexpr int KG_STEPS = KSTEPS / 2;  // ... per K group
 static_assert(TILE == 32 && MI355_MOE_COL_TILE == 64, "moe_tile_kernel is written for 32-row tiles and 64-column workgroups");
-
-struct Layout {
-  int64_t h, y, counts, offsets, perm, tiles, total, max_tiles;
-};
-
-bool moe_layout(int64_t N, int64_t k, int64_t E, int64_t D, int64_t I, Layout* L) {
-  if (N < 1 || k < 1 || E < 1 || D < 1 || I < 1 || N * k > (1 << 30) / 4 || N * k * (D > I ? D : I) > ((int64_t)1 << 40)) return false;
-  const int64_t P = N * k;
-  auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
-  L->max_tiles = (P + TILE - 1) / TILE + E;
-  L->h = 0;
-  L->y = L->h + up(P * I * 4);
-  L->counts = L->y + up(P * D * 4);
-  L->offsets = L->counts + up(E * 4);
-  L->perm = L->offsets + up((E + 1) * 4);
-  L->tiles = L->perm + up(P * 4);
-  L->total = L->tiles + up(L->max_tiles * 16);
-  return true;
-}
 
 // ------------------------------------------------------------------------------------------------------------------------------ router
 __global__ __launch_bounds__(256) void moe_route_kernel(const mi355_moe_route_args a) {
@@ -372,9 +353,13 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* y, const 
   *(float4*)(out + t * ldo + c) = acc;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
+
+void moe_combine_launch(const float* y, const float* weights, int N, int k, int D, const float* shared, int64_t ld_shared, const float* res, int64_t ld_res,
+                        float* out, int64_t ldo, hipStream_t stream) {
+  const int64_t n4 = (int64_t)N * (D / 4);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, y, weights, N, k, D, shared, ld_shared, res, ld_res, out, ldo);
+}
 
 extern "C" int mi355_moe_route(const mi355_moe_route_args* ap, void* stream) {
   MI355_REQUIRE(ap && ap->logits && ap->ids && ap->weights, "moe_route: null tensor");
@@ -411,13 +396,6 @@ extern "C" int mi355_moe_workspace_layout(int32_t N, int32_t k, int32_t E, int32
   MI355_REQUIRE(moe_layout(N, k, E, D, I, &L), "moe_workspace_layout: bad sizes (N = %d, k = %d, E = %d, D = %d, I = %d)", N, k, E, D, I);
   const int64_t v[8] = {L.h, L.y, L.counts, L.offsets, L.perm, L.tiles, L.total, L.max_tiles};
   for (int i = 0; i < 8; ++i) layout[i] = v[i];
-  return MI355_OK;
-}
-
-static int moe_workspace_check(const char* who, int N, int k, int E, int D, int I, const void* ws, int64_t bytes, Layout* L) {
-  MI355_REQUIRE(moe_layout(N, k, E, D, I, L), "%s: bad sizes (N = %d, k = %d, E = %d, D = %d, I = %d)", who, N, k, E, D, I);
-  MI355_REQUIRE(ws && aligned16(ws), "%s: the workspace must be a 16-byte aligned device buffer", who);
-  MI355_REQUIRE(bytes >= L->total, "%s: workspace of %lld bytes is short of mi355_moe_workspace_bytes = %lld", who, (long long)bytes, (long long)L->total);
   return MI355_OK;
 }
 
@@ -501,9 +479,7 @@ extern "C" int mi355_moe_glu(const mi355_moe_glu_args* ap, void* stream) {
   d.Kdim = a.I; d.Ncols = a.D; d.KS = (a.I + 15) / 16; d.NT = (a.D + 31) / 32; d.out = y; d.ldo = a.D;
   const dim3 grid2((unsigned)L.max_tiles, (unsigned)((a.D + MI355_MOE_COL_TILE - 1) / MI355_MOE_COL_TILE));
   hipLaunchKernelGGL(moe_tile_kernel<false>, grid2, dim3(256), 0, (hipStream_t)stream, d);
-  const int64_t n4 = (int64_t)a.N * (a.D / 4);
-  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, a.weights, a.N, a.k, a.D, a.shared,
-                     a.ld_shared, a.res, a.ld_res, a.out, a.ldo);
+  moe_combine_launch(y, a.weights, a.N, a.k, a.D, a.shared, a.ld_shared, a.res, a.ld_res, a.out, a.ldo, (hipStream_t)stream);
   MI355_LAUNCH_CHECK("moe_glu");
   return MI355_OK;
 }

@@ -2,9 +2,16 @@
 device: the router's ``gate_proj`` and the shared experts run on the existing ``linear`` + ``swiglu``; routing, the sort by expert, the routed
 ``SwitchGLU`` and the weighted combine are the kernels of csrc/moe.hip (``ops.moe_route`` / ``ops.switch_glu``).
 
+Quantised checkpoints (MLX's affine `-4bit` / `-8bit`, group 32 / 64 / 128) load as they are: ``sanitize`` stacks the per-expert ``weight`` /
+``scales`` / ``biases``, the routed experts run on the packed codes (csrc/moe_quant.hip: ``ops.PackedQuantizedExperts``), and every dense parameter
+that carries ``.scales`` -- attention, shared experts, dense MLPs, the router's ``gate_proj`` (8 bits in real checkpoints), ``lm_head`` and the
+embedding -- runs on ``ops.qlinear`` / ``ops.dequantize_affine``.  Bits and group size come from the config's ``quantization`` dict (with
+per-path overrides) or, without one, from the shapes.
+
 Parameter names and ``ModelArgs`` fields are the reference's.  ``BailingMoeModel`` / ``Model`` are a host schedule on existing kernels (``rmsnorm``,
 ``linear``, ``head_norm_rope`` / ``partial_rope``, ``flash_attention`` over a ``KVCache``, ``embed_sum``): token ids -> logits for prefill and
-one-row decode steps.  NOT built (each raises by name): quantised experts, hub download, head widths other than 64 / 128, ``rope_scaling``."""
+one-row decode steps.  NOT built (each raises by name): quantised experts at bits 2 / 3 / 5 / 6 or in MLX's non-affine modes (``.scales`` without
+``.biases``), hub download, head widths other than 64 / 128, ``rope_scaling``."""
 from __future__ import annotations
 
 from dataclasses import dataclass, fields
@@ -51,11 +58,14 @@ class ModelArgs:
     topk_group: int = 4
     moe_shared_expert_intermediate_size: Optional[int] = None
     moe_router_enable_shared_expert: bool = True
+    quantization: Optional[dict] = None   # the config's ``quantization`` (or ``quantization_config``): group_size, bits, {path: {...}} overrides
 
     @classmethod
     def from_dict(cls, d: dict) -> "ModelArgs":
         names = {f.name for f in fields(cls)}
         a = cls(**{k: v for k, v in d.items() if k in names})
+        if a.quantization is None:
+            a.quantization = d.get("quantization_config")
         if a.rope_scaling is not None:
             raise NotImplementedError("bailing_moe: rope_scaling is not built")
         if a.hidden_size // a.num_attention_heads not in (64, 128):
@@ -69,12 +79,38 @@ def from_pretrained(*_, **__):
     raise NotImplementedError("bailing_moe: hub download is not built; load a local checkpoint and pass its tensors")
 
 
+QUANT_BITS, QUANT_GROUPS = (4, 8), (32, 64, 128)   # what csrc/qlinear.hip and csrc/moe_quant.hip are built for
+
+
+def resolve_quantization(quantization: Optional[dict], path: str, words: int, groups: int):
+    """(bits, group_size) of the parameter at ``path`` (no ``.weight``) whose packed rows hold ``words`` words beside ``groups`` scales: the entry of
+    ``quantization`` for that path, else its global ``bits`` / ``group_size``, else what the shapes say (``ops.infer_quantization``)."""
+    q = quantization or {}
+    own = q.get(path) or q.get("model." + path)
+    src = own if isinstance(own, dict) else q
+    return ops.infer_quantization(words, groups, group_size=src.get("group_size"), bits=src.get("bits"))
+
+
+def _check_quantized_experts(w, prefix: str, quantization):
+    """What is still not built for ``{prefix}.{weight,scales,biases}``, refused by name."""
+    not_built = "bailing_moe: quantised experts (QuantizedSwitchLinear) "
+    if f"{prefix}.biases" not in w:
+        raise NotImplementedError(not_built + f"in a non-affine mode are not built ({prefix}.scales has no .biases beside it)")
+    wt = w.get(f"{prefix}.weight")
+    if wt is None or wt.dtype not in (torch.uint32, torch.int32):
+        raise NotImplementedError(not_built + f"need packed uint32 codes ({prefix}.weight is {None if wt is None else wt.dtype})")
+    try:
+        bits, group = resolve_quantization(quantization, prefix, wt.shape[-1], w[f"{prefix}.scales"].shape[-1])
+    except (ValueError, AssertionError) as err:
+        raise NotImplementedError(not_built + f"at {prefix}: {err}") from None
+    if bits not in QUANT_BITS or group not in QUANT_GROUPS:
+        raise NotImplementedError(not_built + f"with bits = {bits}, group_size = {group} are not built (bits {QUANT_BITS}, groups {QUANT_GROUPS} are)")
+
+
 def sanitize(weights: Dict[str, torch.Tensor], args: ModelArgs) -> Dict[str, torch.Tensor]:
-    """``Model.sanitize`` of the reference: per-expert tensors stacked into ``switch_mlp.*``, the router renamed to ``gate.gate_proj.*``, the tied
-    head dropped, ``norm_head`` applied.  Quantised checkpoints (``.scales`` / ``.biases`` beside an expert weight) are refused by name."""
+    """``Model.sanitize`` of the reference: per-expert tensors (``weight`` / ``scales`` / ``biases`` / ``bias``) stacked into ``switch_mlp.*``, the
+    router renamed to ``gate.gate_proj.*``, the tied head dropped, ``norm_head`` applied.  Quantised experts outside what is built are refused by name."""
     w = dict(weights)
-    if any(k.endswith((".scales", ".biases")) and ".mlp." in k for k in w):
-        raise NotImplementedError("bailing_moe: quantised experts (QuantizedSwitchLinear) are not built")
     if args.tie_word_embeddings:
         w.pop("lm_head.weight", None)
     if args.norm_head and "lm_head.weight" in w:
@@ -83,22 +119,55 @@ def sanitize(weights: Dict[str, torch.Tensor], args: ModelArgs) -> Dict[str, tor
     for l in range(args.first_k_dense_replace, args.num_hidden_layers):
         p = f"model.layers.{l}.mlp"
         for m in ("gate_proj", "down_proj", "up_proj"):
-            for k in ("weight", "bias"):
+            for k in ("weight", "scales", "biases", "bias"):
                 if f"{p}.experts.0.{m}.{k}" in w:
                     w[f"{p}.switch_mlp.{m}.{k}"] = torch.stack([w.pop(f"{p}.experts.{e}.{m}.{k}") for e in range(args.num_experts)])
-        for k in ("weight", "bias"):
+            if f"{p}.switch_mlp.{m}.scales" in w:
+                _check_quantized_experts(w, f"{p}.switch_mlp.{m}", args.quantization)
+        for k in ("weight", "scales", "biases", "bias"):
             if f"{p}.gate.{k}" in w:
                 w[f"{p}.gate.gate_proj.{k}"] = w.pop(f"{p}.gate.{k}")
     return w
 
 
-class SwitchGLU:
-    """``switch_mlp.{gate,up,down}_proj``: the packed expert images.  ``__call__`` is the routed FFN with its combine (``ops.switch_glu``)."""
+def _rows_of(weights, name: str, pick=None) -> Dict[str, torch.Tensor]:
+    """The row tensors of parameter ``name`` (``weight``, ``bias`` and, when quantised, ``scales`` / ``biases``), each with the row operation ``pick``
+    applied: a row pick, split or interleave acts on the packed words and on the pair rows as it does on float rows."""
+    t = {k: weights[f"{name}.{k}"] for k in ("weight", "scales", "biases", "bias") if weights.get(f"{name}.{k}") is not None}
+    return t if pick is None else {k: pick(v) for k, v in t.items()}
 
-    def __init__(self, weights, prefix: str, device):
-        if f"{prefix}gate_proj.scales" in weights:
-            raise NotImplementedError("bailing_moe: quantised experts (QuantizedSwitchLinear) are not built")
+
+def _make_lin(t: Dict[str, torch.Tensor], device, quantization, path: str):
+    """A dense Linear from its row tensors: float -> ``make_lin``; with ``scales`` -> the packed codes for ``ops.qlinear``."""
+    if "scales" not in t:
+        return make_lin(t["weight"], t.get("bias"), device)
+    bits, group = resolve_quantization(quantization, path, t["weight"].shape[-1], t["scales"].shape[-1])
+    return ops.pack_quantized(t["weight"], t["scales"], t["biases"], t.get("bias"), device, group_size=group, bits=bits)
+
+
+def _linear(x: torch.Tensor, l, y: torch.Tensor, *, res: Optional[torch.Tensor] = None):
+    """``linear`` on [B, L, C] views for either kind of image."""
+    if not isinstance(l, ops.QuantizedLinear):
+        return linear(x, l, y, res=res)
+    for b in range(x.shape[0]):
+        ops.qlinear(x[b], l, y[b], res=None if res is None else res[b])
+    return y
+
+
+class SwitchGLU:
+    """``switch_mlp.{gate,up,down}_proj``: the packed expert images (float) or the packed codes (a quantised checkpoint).  ``__call__`` is the routed
+    FFN with its combine (``ops.switch_glu``)."""
+
+    def __init__(self, weights, prefix: str, device, quantization: Optional[dict] = None):
         g = lambda n: weights.get(f"{prefix}{n}")
+        if g("gate_proj.scales") is not None:
+            packed = []
+            for m in ("gate_proj", "up_proj", "down_proj"):
+                bits, group = resolve_quantization(quantization, f"{prefix}{m}", g(f"{m}.weight").shape[-1], g(f"{m}.scales").shape[-1])
+                packed.append(ops.pack_quantized_switch_linear(g(f"{m}.weight"), g(f"{m}.scales"), g(f"{m}.biases"), g(f"{m}.bias"), device,
+                                                               group_size=group, bits=bits))
+            self.experts = ops.PackedQuantizedExperts(*packed)
+            return
         self.experts = ops.PackedExperts.pack(g("gate_proj.weight"), g("up_proj.weight"), g("down_proj.weight"), device, gate_b=g("gate_proj.bias"),
                                               up_b=g("up_proj.bias"), down_b=g("down_proj.bias"))
 
@@ -109,16 +178,18 @@ class SwitchGLU:
 class BailingMoeGate:
     def __init__(self, args: ModelArgs, weights, prefix: str, device):
         self.args = args
-        self.lin = make_lin(weights[f"{prefix}gate_proj.weight"], weights.get(f"{prefix}gate_proj.bias"), device)
+        self.lin = _make_lin(_rows_of(weights, f"{prefix}gate_proj"), device, args.quantization, f"{prefix}gate_proj")
         b = weights.get(f"{prefix}expert_bias") if args.moe_router_enable_expert_bias else None
         self.expert_bias = None if b is None else b.to(device=device, dtype=torch.float32).contiguous()
 
-    def __call__(self, x: torch.Tensor):
-        """x [B, L, D] -> (ids [B L, k] int32, weights [B L, k])."""
+    def __call__(self, x: torch.Tensor, trace: Optional[dict] = None):
+        """x [B, L, D] -> (ids [B L, k] int32, weights [B L, k]); ``trace`` receives the router ``logits`` [B L, E]."""
         a = self.args
         B, L, _ = x.shape
         logits = torch.empty(B, L, a.num_experts, device=x.device)
-        linear(x, self.lin, logits)
+        _linear(x, self.lin, logits)
+        if trace is not None:
+            trace["logits"] = logits.view(B * L, a.num_experts)
         return ops.moe_route(logits.view(B * L, a.num_experts), a.num_experts_per_tok, expert_bias=self.expert_bias, score_function=a.score_function,
                              n_group=a.n_group, topk_group=a.topk_group, norm_topk_prob=a.norm_topk_prob, routed_scaling_factor=a.routed_scaling_factor)
 
@@ -126,35 +197,35 @@ class BailingMoeGate:
 class BailingMoeMLP:
     """down(swiglu(gate(x), up(x))) on the dense kernels: gate and up rows interleaved into one image for ``ops.swiglu``."""
 
-    def __init__(self, weights, prefix: str, device):
-        wg, wu = weights[f"{prefix}gate_proj.weight"], weights[f"{prefix}up_proj.weight"]
-        bg, bu = weights.get(f"{prefix}gate_proj.bias"), weights.get(f"{prefix}up_proj.bias")
-        self.inter = wg.shape[0]
+    def __init__(self, weights, prefix: str, device, quantization: Optional[dict] = None):
+        tg, tu = _rows_of(weights, f"{prefix}gate_proj"), _rows_of(weights, f"{prefix}up_proj")
+        assert tg.keys() == tu.keys(), f"bailing_moe: {prefix}gate_proj and up_proj differ in kind ({sorted(tg)} / {sorted(tu)})"
+        self.inter = tg["weight"].shape[0]
         inter = lambda a, b: torch.stack([a, b], 1).reshape(2 * a.shape[0], *a.shape[1:])
-        self.gate_up = make_lin(inter(wg, wu), None if bg is None else inter(bg, bu), device)
-        self.down = make_lin(weights[f"{prefix}down_proj.weight"], weights.get(f"{prefix}down_proj.bias"), device)
+        self.gate_up = _make_lin({k: inter(tg[k], tu[k]) for k in tg}, device, quantization, f"{prefix}gate_proj")
+        self.down = _make_lin(_rows_of(weights, f"{prefix}down_proj"), device, quantization, f"{prefix}down_proj")
 
     def __call__(self, x: torch.Tensor, out: torch.Tensor, *, res: Optional[torch.Tensor] = None):
         B, L, _ = x.shape
         gu = torch.empty(B, L, 2 * self.inter, device=x.device)
         h = torch.empty(B, L, self.inter, device=x.device)
-        linear(x, self.gate_up, gu)
+        _linear(x, self.gate_up, gu)
         ops.swiglu(gu, h)
-        return linear(h, self.down, out, res=res)
+        return _linear(h, self.down, out, res=res)
 
 
 class BailingMoeSparseMoeBlock:
     def __init__(self, args: ModelArgs, weights, prefix: str, device):
         self.args = args
-        self.switch_mlp = SwitchGLU(weights, f"{prefix}switch_mlp.", device)
+        self.switch_mlp = SwitchGLU(weights, f"{prefix}switch_mlp.", device, args.quantization)
         self.gate = BailingMoeGate(args, weights, f"{prefix}gate.", device)
         on = args.num_shared_experts > 0 and args.moe_router_enable_shared_expert
-        self.shared_experts = BailingMoeMLP(weights, f"{prefix}shared_experts.", device) if on else None
+        self.shared_experts = BailingMoeMLP(weights, f"{prefix}shared_experts.", device, args.quantization) if on else None
 
     def __call__(self, x: torch.Tensor, out: torch.Tensor, *, res: Optional[torch.Tensor] = None, trace: Optional[dict] = None):
         """x / out / res [B, L, D]: out = sum_slot weight * expert(x) + shared_experts(x) + res."""
         B, L, D = x.shape
-        ids, wts = self.gate(x)
+        ids, wts = self.gate(x, trace)
         shared = None
         if self.shared_experts is not None:
             shared = self.shared_experts(x, torch.empty(B, L, D, device=x.device)).view(B * L, D)
@@ -178,12 +249,11 @@ class _Attention:
         if self.rot < dh:
             src[0:self.rot:2], src[1:self.rot:2] = torch.arange(self.rot // 2), torch.arange(self.rot // 2, self.rot)
         rows = lambda n: (torch.arange(n)[:, None] * dh + src[None, :]).reshape(-1)
-        w, b = weights[f"{prefix}query_key_value.weight"], weights.get(f"{prefix}query_key_value.bias")
         pick = torch.cat([rows(H), H * dh + rows(G), (H + G) * dh + torch.arange(G * dh)])
-        w, b = w[pick], None if b is None else b[pick]
-        self.wq = make_lin(w[:H * dh], None if b is None else b[:H * dh], device)
-        self.wkv = make_lin(w[H * dh:], None if b is None else b[H * dh:], device)
-        self.dense = make_lin(weights[f"{prefix}dense.weight"], weights.get(f"{prefix}dense.bias"), device)
+        qkv, quant = f"{prefix}query_key_value", args.quantization
+        self.wq = _make_lin(_rows_of(weights, qkv, lambda t: t[pick][:H * dh]), device, quant, qkv)
+        self.wkv = _make_lin(_rows_of(weights, qkv, lambda t: t[pick][H * dh:]), device, quant, qkv)
+        self.dense = _make_lin(_rows_of(weights, f"{prefix}dense"), device, quant, f"{prefix}dense")
         nw = lambda n: weights[f"{prefix}{n}_layernorm.weight"][src].to(device=device, dtype=torch.float32).contiguous() if args.use_qk_norm else None
         self.qn, self.kn = nw("query"), nw("key")
         self.cos, self.sin = ops.moonshine_rope_tables(self.rot, args.max_position_embeddings, base=args.rope_theta, device=device)
@@ -197,8 +267,8 @@ class _Attention:
             raise ValueError(f"bailing_moe: position {off + L - 1} is past max_position_embeddings = {self.cos.shape[0]}")
         slot = kvc.reserve(B, L)
         q, att = torch.empty(B, L, H * dh, device=h.device), torch.empty(B, L, H * dh, device=h.device)
-        linear(h, self.wq, q)
-        linear(h, self.wkv, slot)
+        _linear(h, self.wq, q)
+        _linear(h, self.wkv, slot)
         ks = slot[:, :, :G * dh]
         if self.rot == dh:
             ops.head_norm_rope(q, q, heads=H, dh=dh, norm_weight=self.qn, eps=self.eps, cos=self.cos, sin=self.sin, pos0=off, second=(ks, ks, G, self.kn))
@@ -207,7 +277,7 @@ class _Attention:
                 ops.head_norm_rope(q, q, heads=H, dh=dh, norm_weight=self.qn, eps=self.eps, second=(ks, ks, G, self.kn))
             ops.partial_rope(q, q, heads=H, dh=dh, rot=self.rot, cos=self.cos, sin=self.sin, pos0=off, second=(ks, ks, G))
         ops.flash_attention(q, kvc.keys, kvc.values, att, heads=H, kv_heads=G, dh=dh, causal=True)
-        return linear(att, self.dense, x, res=x)
+        return _linear(att, self.dense, x, res=x)
 
 
 class BailingMoeModel:
@@ -215,12 +285,13 @@ class BailingMoeModel:
         ops.require_gpu()
         self.args, self.device = args, torch.device(device)
         vec = lambda n: weights[prefix + n].to(device=self.device, dtype=torch.float32).contiguous()
-        self.word_embeddings = vec("word_embeddings.weight")
+        emb = _rows_of(weights, prefix + "word_embeddings")
+        self.word_embeddings = _make_lin(emb, self.device, args.quantization, prefix + "word_embeddings") if "scales" in emb else vec("word_embeddings.weight")
         self.layers = []
         for i in range(args.num_hidden_layers):
             p = f"{prefix}layers.{i}."
             sparse = args.num_experts is not None and i >= args.first_k_dense_replace
-            mlp = BailingMoeSparseMoeBlock(args, weights, p + "mlp.", self.device) if sparse else BailingMoeMLP(weights, p + "mlp.", self.device)
+            mlp = BailingMoeSparseMoeBlock(args, weights, p + "mlp.", self.device) if sparse else BailingMoeMLP(weights, p + "mlp.", self.device, args.quantization)
             self.layers.append((vec(f"layers.{i}.input_layernorm.weight"), _Attention(args, weights, p + "attention.", self.device),
                                 vec(f"layers.{i}.post_attention_layernorm.weight"), mlp))
         self.norm = vec("norm.weight")
@@ -235,7 +306,11 @@ class BailingMoeModel:
         eps = self.args.rms_norm_eps
         cache = self.make_cache() if cache is None else cache
         x = torch.empty(B, L, self.args.hidden_size, device=self.device)
-        ops.embed_sum(self.word_embeddings, inputs.to(device=self.device, dtype=torch.int32).reshape(B, L, 1), x)
+        tokens = inputs.to(device=self.device, dtype=torch.int32)
+        if isinstance(self.word_embeddings, ops.QuantizedLinear):   # the quantised table: a row gather that dequantises
+            ops.dequantize_affine(self.word_embeddings, tokens, out=x.view(B * L, -1))
+        else:
+            ops.embed_sum(self.word_embeddings, tokens.reshape(B, L, 1), x)
         h = torch.empty_like(x)
         for i, ((ln1, attn, ln2, mlp), kvc) in enumerate(zip(self.layers, cache)):
             attn(ops.rmsnorm(x, h, ln1, eps=eps), x, kvc)
@@ -244,7 +319,7 @@ class BailingMoeModel:
                 t = {} if trace is not None else None
                 mlp(h, x, res=x, trace=t)
                 if trace is not None:
-                    trace[f"ids{i}"], trace[f"weights{i}"] = t["ids"], t["weights"]
+                    trace[f"ids{i}"], trace[f"weights{i}"], trace[f"router_logits{i}"] = t["ids"], t["weights"], t["logits"]
             else:
                 mlp(h, x, res=x)
             if trace is not None:
@@ -258,15 +333,19 @@ class Model:
     def __init__(self, args: ModelArgs, weights, device="cuda:0"):
         self.args = args
         self.model = BailingMoeModel(args, weights, device)
-        head = weights["model.word_embeddings.weight"] if args.tie_word_embeddings else weights["lm_head.weight"]
-        self.lm_head = make_lin(head, None, self.model.device)
+        if args.tie_word_embeddings and isinstance(self.model.word_embeddings, ops.QuantizedLinear):
+            self.lm_head = self.model.word_embeddings   # the quantised table is also the head
+        else:
+            name = "model.word_embeddings" if args.tie_word_embeddings else "lm_head"
+            head = {k: v for k, v in _rows_of(weights, name).items() if k != "bias"}
+            self.lm_head = _make_lin(head, self.model.device, args.quantization, name)
 
     def make_cache(self):
         return self.model.make_cache()
 
     def __call__(self, inputs: torch.Tensor, cache=None, trace: Optional[dict] = None) -> torch.Tensor:
         h = self.model(inputs, cache, trace)
-        return linear(h, self.lm_head, torch.empty(*h.shape[:2], self.args.vocab_size, device=h.device))
+        return _linear(h, self.lm_head, torch.empty(*h.shape[:2], self.args.vocab_size, device=h.device))
 
 
 def make_moe_weights(args: ModelArgs, seed: int = 0) -> Dict[str, torch.Tensor]:
