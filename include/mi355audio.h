@@ -1902,6 +1902,66 @@ typedef struct {
 } mi355_dequantize_affine_args;
 int mi355_dequantize_affine(const mi355_dequantize_affine_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Linear on MLX's block-scaled floating-point weights (the `-mxfp4` / `-nvfp4` / `-mxfp8` checkpoints; qlinear_mx.hip).  Added to ABI 37 (new
+ * structs and functions only).  The format, stated here once:
+ *   q       uint32 [N, K bits / 32], element k of a row in word k / (32 / bits) at bit bits * (k % (32 / bits)): the packing of the affine mode
+ *   scales  uint8 [N, K / g], one byte per group; there are no `.biases` and no tensor-level scale
+ *   mode                 g   bits  element                                                      scale byte
+ *   MI355_QMODE_MXFP4    32  4     E2M1: bit 3 sign, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6      E8M0: 2^(b - 127)
+ *   MI355_QMODE_NVFP4    16  4     E2M1                                                         E4M3, taken as its value
+ *   MI355_QMODE_MXFP8    32  8     E4M3 (fn: no infinities, bias 7, subnormals to 2^-9, max 448) E8M0
+ *   w[n, k] = value(code) * value(scale[n, k / g]);   y[m, n] = epilogue( sum_k x[m, k] * w[n, k] )
+ * Unspecified: an E8M0 byte of 255, the E4M3 NaN codes 0x7F / 0xFF, a negative nvfp4 scale (MLX's quantiser emits none of them).
+ * There is no zero term, hence no X[m, group] sums.  The codes leave HBM as they are and are decoded in registers by the gfx950 conversions
+ * (v_cvt_scalef32_pk_{f16,f32}_{fp4,fp8}, scale operand 1: byte j of a word gives codes 2 j (low half) and 2 j + 1); every element is an exact
+ * fp16 value.  Every sum runs in a fixed order: two calls on the same bytes give the same bits.
+ *   1 .. 8 rows   stream form: a lane owns runs of 128 consecutive codes of one weight row (four 32-code steps, 16-byte loads) and fetches
+ *                 the run's scale bytes as one or two 32-bit loads; codes to fp32, S per group, acc = fmaf(scale, S, acc); eight lanes per
+ *                 output column, K split over the four waves (eight columns a workgroup)
+ *   9 rows and up tile form: v_mfma_f32_16x16x32_f16, the codes as the A operand; x split once per workgroup into fp16 hi + lo images in
+ *                 LDS.  mxfp4 / mxfp8: one group is one K step, two MFMAs (hi, lo) into a zeroed tile, then acc = fmaf(2^e, tile, acc) in
+ *                 the C layout (exact: a power of two); the scale bytes of four groups arrive as one 32-bit load per column.  nvfp4: a K
+ *                 step holds two groups; the E4M3 scale is multiplied into the operand by one packed fp16 multiply per register (E2M1 x
+ *                 E4M3 is an exact normal fp16 value) and the MFMAs accumulate directly.  16 columns x 16 or 32 rows a workgroup.
+ * A (mode, bits, group_size) triple other than the three above, K % 32 != 0 (K % 16 for nvfp4) and norm / glu / rope_cos / x_ids are
+ * MI355_ERR_UNSUPPORTED with the value named; null pointers, sizes and alignments MI355_ERR_ARG (x and q 16-byte aligned, ldx % 4 == 0).
+ * A refused call launches nothing and leaves every output untouched.  Epilogue: the one of mi355_gemv, as in mi355_qlinear.
+ * ------------------------------------------------------------------------------------------ */
+enum { MI355_QMODE_MXFP4 = 1, MI355_QMODE_NVFP4 = 2, MI355_QMODE_MXFP8 = 3 };
+typedef struct {
+  const float* x; int32_t ldx; int32_t M; int32_t K; int32_t N;
+  const uint32_t* q; const uint8_t* scales; int32_t mode; int32_t bits; int32_t group_size;
+  const float* bias;       /* [N] nullable */
+  int32_t post_act; float post_slope;
+  const float* colscale;   /* [N] nullable */
+  const float* res; int32_t ldr;
+  float out_scale;         /* 0 => 1 */
+  float* y; int32_t ldy;
+  void* y2; int32_t ldy2; int32_t split; int32_t y2_dtype;   /* columns n >= split go to y2[m, n - split] in MI355_KV_* */
+  int32_t norm; int32_t glu; const float* rope_cos; const int32_t* x_ids;   /* not built: must be 0 / null */
+} mi355_qlinear_mx_args;
+int mi355_qlinear_mx(const mi355_qlinear_mx_args* a, void* stream);
+
+/* What mi355_qlinear_mx would run for `a`, decided without touching the device or dereferencing a pointer of `a`: the same validation, then
+ * form MI355_QLINEAR_STREAM / MI355_QLINEAR_TILE, the mode, rows (the rows template 1, 2, 4, 8 or the row block 16, 32), the grid, the
+ * dynamic LDS bytes and the input columns staged per chunk. */
+typedef struct {
+  int32_t form; int32_t mode; int32_t bits; int32_t group_size; int32_t rows;
+  int32_t grid_x; int32_t grid_y; int32_t lds_bytes; int32_t chunk_k;
+} mi355_qlinear_mx_route_info;
+int mi355_qlinear_mx_route(const mi355_qlinear_mx_args* a, mi355_qlinear_mx_route_info* out);
+
+/* Floats of the same image: out[r, k] = float32(value(code)) * float32(value(scale)) + add[r % add_rows, k], the product rounded once in
+ * float32 and the sum once more (no fused multiply-add).  rows / add / out as in mi355_dequantize_affine; same format rules as above. */
+typedef struct {
+  const uint32_t* q; const uint8_t* scales; int32_t mode; int32_t bits; int32_t group_size; int32_t N; int32_t K;
+  const int32_t* rows; int32_t n_rows;
+  const float* add; int32_t ld_add; int32_t add_rows;
+  float* out; int32_t ldo;
+} mi355_dequantize_mx_args;
+int mi355_dequantize_mx(const mi355_dequantize_mx_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2416,7 +2416,7 @@ def _rows2d(t: torch.Tensor, cols: int) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), cols)
 
 
-def qlinear(x: torch.Tensor, ql: QuantizedLinear, y: torch.Tensor, *, post_act: int = ACT_NONE, post_slope: float = 0.0,
+def qlinear(x: torch.Tensor, ql: "QuantizedLinear | QuantizedLinearMX", y: torch.Tensor, *, post_act: int = ACT_NONE, post_slope: float = 0.0,
             res: Optional[torch.Tensor] = None, colscale: Optional[torch.Tensor] = None, out_scale: float = 1.0, y2: Optional[torch.Tensor] = None,
             use_bias: bool = True):
     """y[m, :] = epilogue(x[m, :] @ dequantised(W)^T) on the packed codes (``mi355_qlinear``): 1..8 rows the stream form, 9 and up the tile form.
@@ -2425,16 +2425,18 @@ def qlinear(x: torch.Tensor, ql: QuantizedLinear, y: torch.Tensor, *, post_act: 
     M = x.shape[0]
     n_y = ql.n if y2 is None else ql.n - y2.shape[1]
     assert y.shape[0] == M, (x.shape, y.shape)
-    kw = dict(x=_ptr(x), ldx=_rows2d(x, ql.k), M=M, K=ql.k, N=ql.n, q=_ptr(ql.q), sz=_ptr(ql.sz), bits=ql.bits, group_size=ql.group_size,
-              sz_dtype=KV_DTYPES[ql.sz.dtype], bias=_ptr(ql.bias) if use_bias else None, post_act=post_act, post_slope=post_slope,
+    mx = isinstance(ql, QuantizedLinearMX)   # the block-scaled floating-point modes: mi355_qlinear_mx, scale bytes instead of (scale, zero) pairs
+    kw = dict(x=_ptr(x), ldx=_rows2d(x, ql.k), M=M, K=ql.k, N=ql.n, q=_ptr(ql.q), bits=ql.bits, group_size=ql.group_size,
+              bias=_ptr(ql.bias) if use_bias else None, post_act=post_act, post_slope=post_slope,
               colscale=_ptr(colscale), out_scale=out_scale, y=_ptr(y), ldy=_rows2d(y, n_y))
+    kw.update(dict(scales=_ptr(ql.scales), mode=QMODES[ql.mode][0]) if mx else dict(sz=_ptr(ql.sz), sz_dtype=KV_DTYPES[ql.sz.dtype]))
     if res is not None:
         assert res.dtype == torch.float32 and res.shape[0] == M
         kw.update(res=_ptr(res), ldr=_rows2d(res, ql.n))
     if y2 is not None:
         assert y2.shape[0] == M and y2.dtype in KV_DTYPES
         kw.update(y2=_ptr(y2), ldy2=_rows2d(y2, ql.n - n_y), split=n_y, y2_dtype=KV_DTYPES[y2.dtype])
-    _lib.call_struct("mi355_qlinear", "mi355_qlinear_args", _stream(), **kw)
+    _lib.call_struct("mi355_qlinear_mx" if mx else "mi355_qlinear", "mi355_qlinear_mx_args" if mx else "mi355_qlinear_args", _stream(), **kw)
     return y
 
 
@@ -2496,6 +2498,142 @@ def quantize_affine(w: torch.Tensor, group_size: int = 64, bits: int = 4) -> Tup
     zero = lo.to(w.dtype)
     codes = torch.round((g - zero.float()[..., None]) / scale.float()[..., None]).clamp_(0, (1 << bits) - 1).to(torch.int64)
     return pack_codes(codes.reshape(n, k), bits), scale, zero
+
+
+# --------------------------------------------------------------------------------------- MLX mxfp4 / nvfp4 / mxfp8 (qlinear_mx.hip)
+# The format (stated once more in include/mi355audio.h: mi355_qlinear_mx).  ``weight`` uint32 [N, K bits / 32] packed as in the affine mode
+# (``pack_codes`` / ``unpack_codes`` apply), ``scales`` uint8 [N, K / g], no ``.biases``, no tensor-level scale:
+#   mode    g   bits  element                                                        scale byte
+#   mxfp4   32  4     E2M1: bit 3 sign, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6        E8M0: 2^(b - 127)
+#   nvfp4   16  4     E2M1                                                           E4M3, taken as its value
+#   mxfp8   32  8     E4M3 (fn: no infinities, bias 7, subnormals to 2^-9, max 448)  E8M0
+# w[n, k] = value(code) * value(scale[n, k / g]).  Unspecified: an E8M0 byte of 255, the E4M3 NaN codes, a negative nvfp4 scale.
+QMODES = {"mxfp4": (1, 4, 32), "nvfp4": (2, 4, 16), "mxfp8": (3, 8, 32)}   # name -> (MI355_QMODE_*, bits, group_size)
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+@dataclass
+class QuantizedLinearMX:
+    """One quantised Linear / Embedding of a `-mxfp4` / `-nvfp4` / `-mxfp8` MLX checkpoint on the device, words and scale bytes as they are in the file."""
+
+    q: torch.Tensor        # int32 [N, K * bits / 32]
+    scales: torch.Tensor   # uint8 [N, K / group_size]
+    bias: Optional[torch.Tensor]
+    n: int
+    k: int
+    mode: str
+    bits: int
+    group_size: int
+
+
+def mx_code_values(codes: torch.Tensor, mode: str) -> torch.Tensor:
+    """float32 values of element codes (integers 0 .. 2^bits - 1) of ``mode``, in plain torch."""
+    if QMODES[mode][1] == 8:
+        return codes.to(torch.uint8).view(torch.float8_e4m3fn).to(torch.float32)
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=codes.device)[(codes & 7).long()]
+    return torch.where((codes & 8) != 0, -mag, mag)
+
+
+def mx_scale_values(scales: torch.Tensor, mode: str) -> torch.Tensor:
+    """float32 values of scale bytes: E4M3 at nvfp4, else E8M0 = 2^(b - 127)."""
+    if mode == "nvfp4":
+        return scales.to(torch.uint8).view(torch.float8_e4m3fn).to(torch.float32)
+    return torch.ldexp(torch.ones((), dtype=torch.float32, device=scales.device), scales.to(torch.int32) - 127)
+
+
+def infer_quantization_mx(words_per_row: int, groups_per_row: int, *, mode: Optional[str] = None) -> Tuple[str, int, int]:
+    """(mode, bits, group_size) of a packed ``.weight`` [N, words] beside uint8 ``.scales`` [N, groups] without ``.biases``: the shapes alone name
+    the mode (32 words / groups = 128 mxfp4, 64 nvfp4, 256 mxfp8).  ``mode`` (the checkpoint's ``quantization.mode``) must agree."""
+    assert groups_per_row > 0
+    prod = 32 * words_per_row / groups_per_row
+    found = {128: "mxfp4", 64: "nvfp4", 256: "mxfp8"}.get(prod)
+    if found is None:
+        raise ValueError(f"a [N, {words_per_row}] weight with [N, {groups_per_row}] uint8 scales is none of mxfp4 / nvfp4 / mxfp8")
+    if mode is not None and mode != found:
+        raise ValueError(f"quantization mode {mode!r} contradicts the shapes: a [N, {words_per_row}] weight with [N, {groups_per_row}] uint8 scales is {found}")
+    return (found, *QMODES[found][1:])
+
+
+def pack_quantized_mx(weight_u32: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor], device, *, mode: Optional[str] = None) -> QuantizedLinearMX:
+    """The device image of one MX parameter: ``weight_u32`` uint32 [N, K bits / 32], ``scales`` uint8 [N, K / g], ``bias`` the Linear's own or None."""
+    q = _words(weight_u32)
+    assert scales.dtype == torch.uint8 and scales.dim() == 2 and scales.shape[0] == q.shape[0], (q.shape, scales.shape, scales.dtype)
+    mode, bits, g = infer_quantization_mx(q.shape[1], scales.shape[1], mode=mode)
+    bd = None if bias is None else bias.detach().to(torch.float32).contiguous().to(device)
+    return QuantizedLinearMX(q.to(device), scales.contiguous().to(device), bd, q.shape[0], scales.shape[1] * g, mode, bits, g)
+
+
+def qlinear_mx(x: torch.Tensor, ql: QuantizedLinearMX, y: torch.Tensor, **kw):
+    """``qlinear`` on an MX image (``mi355_qlinear_mx``); the same keywords."""
+    assert isinstance(ql, QuantizedLinearMX)
+    return qlinear(x, ql, y, **kw)
+
+
+def qlinear_mx_route(M: int, N: int, K: int, mode: str, **fields) -> dict:
+    """What ``qlinear_mx`` would run for these sizes (``mi355_qlinear_mx_route``), or its refusal as ``Mi355Error``.  Needs no device: the addresses
+    are made up and never read.  ``fields`` overrides any other struct field."""
+    m, bits, g = QMODES[mode]
+    kw = dict(x=0x10000000, ldx=K, M=M, K=K, N=N, q=0x20000000, scales=0x30000000, mode=m, bits=bits, group_size=g, y=0x40000000, ldy=N)
+    kw.update(fields)
+    return _lib.call_struct_out("mi355_qlinear_mx_route", "mi355_qlinear_mx_args", "mi355_qlinear_mx_route_info", **kw)
+
+
+def dequantize_mx(ql: QuantizedLinearMX, rows: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
+                  add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Floats of an MX parameter (``mi355_dequantize_mx``), whole or the rows ``rows``: float32(value(code)) * float32(value(scale)), rounded once,
+    bit-equal to ``mx_code_values * mx_scale_values``; ``add`` as in ``dequantize_affine``."""
+    if rows is not None:
+        rows = rows.reshape(-1).contiguous()
+        assert rows.dtype == torch.int32 and rows.is_cuda
+    n_rows = ql.n if rows is None else rows.numel()
+    out = torch.empty((n_rows, ql.k), dtype=torch.float32, device=ql.q.device) if out is None else out
+    assert out.dtype == torch.float32 and out.shape[0] == n_rows
+    kw = dict(q=_ptr(ql.q), scales=_ptr(ql.scales), mode=QMODES[ql.mode][0], bits=ql.bits, group_size=ql.group_size, N=ql.n, K=ql.k, rows=_ptr(rows),
+              n_rows=n_rows, out=_ptr(out), ldo=_rows2d(out, ql.k))
+    if add is not None:
+        assert add.dtype == torch.float32
+        kw.update(add=_ptr(add), ld_add=_rows2d(add, ql.k), add_rows=add.shape[0])
+    _lib.call_struct("mi355_dequantize_mx", "mi355_dequantize_mx_args", _stream(), **kw)
+    return out
+
+
+def dequantize_packed(ql, rows: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
+    """``dequantize_affine`` or ``dequantize_mx``, by the container."""
+    return (dequantize_mx if isinstance(ql, QuantizedLinearMX) else dequantize_affine)(ql, rows, **kw)
+
+
+def _round_e2m1(a: torch.Tensor) -> torch.Tensor:
+    """Magnitudes (clipped to 6) -> the nearest E2M1 magnitude code 0 .. 7, ties to the code with an even mantissa."""
+    mids = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)   # between codes i and i + 1: a tie stays at an even i and moves up from an odd one
+    return sum(((a > m) if i % 2 == 0 else (a >= m)).to(torch.int64) for i, m in enumerate(mids))
+
+
+def quantize_mx(w: torch.Tensor, mode: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(weight uint32 [N, K bits / 32], scales uint8 [N, K / g])`` of ``mode`` in plain torch, for producing checkpoints.  mxfp4 / mxfp8: the E8M0
+    scale is the smallest power of two that brings the group's largest magnitude under the element format's largest (6 / 448); nvfp4: the E4M3
+    scale is max / 6 rounded to E4M3.  Codes are round-to-nearest-even onto the element grid (clipped to its largest).  Only the DEQUANTISATION is
+    pinned to MLX; the quantiser's choice of scale is ours, and ``w`` comes back within half an element step."""
+    _, bits, g = QMODES[mode]
+    assert w.dim() == 2 and w.shape[1] % g == 0 and w.is_floating_point()
+    n, k = w.shape
+    v = w.detach().to(torch.float32).reshape(n, k // g, g)
+    amax = v.abs().amax(-1)
+    if mode == "nvfp4":
+        sb = torch.where(amax > 0, (amax / 6.0).clamp(2.0 ** -9, 448.0), amax).to(torch.float8_e4m3fn)   # never rounds a live group's scale to zero
+        scale = sb.to(torch.float32)
+        scales = sb.view(torch.uint8)
+    else:
+        m, x = torch.frexp(amax)   # amax = m 2^x, m in [0.5, 1); 6 = 0.75 * 2^3, 448 = 0.875 * 2^9
+        mm, xm = (0.75, 3) if bits == 4 else (0.875, 9)
+        e = (x - xm + (m > mm).to(x.dtype)).clamp(-127, 127)
+        scale = torch.ldexp(torch.ones_like(amax), e)
+        scales = (e + 127).to(torch.uint8)
+    t = torch.where(scale[..., None] > 0, v / scale[..., None].clamp_min(2.0 ** -126), torch.zeros_like(v))
+    if bits == 8:
+        codes = t.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8).to(torch.int64)
+    else:
+        codes = _round_e2m1(t.abs().clamp_max(6.0)) | ((t < 0).to(torch.int64) << 3)
+    return pack_codes(codes.reshape(n, k), bits), scales
 
 
 # --------------------------------------------------------------------------------------- quantised expert weights (moe_quant.hip)

@@ -81,7 +81,9 @@ class WhisperEngine:
                  kv_dtype: torch.dtype = torch.float16, pos_dtype: torch.dtype = torch.float16, quantized: Optional[Dict[str, tuple]] = None,
                  quantization: Optional[dict] = None):
         """``quantized``: {parameter prefix: (weight uint32, scales, biases)} of the quantised Linears / Embedding of an MLX checkpoint (``weights`` then
-        holds only their ``.bias``); ``quantization``: optional {"group_size", "bits"} where the shapes alone leave two readings (``ops.infer_quantization``)."""
+        holds only their ``.bias``); ``quantization``: the checkpoint's optional {"group_size", "bits", "mode"}: group_size / bits settle an affine parameter whose shapes leave
+        two readings (``ops.infer_quantization``); mode ("affine", "mxfp4", "nvfp4", "mxfp8") must agree with what the shapes say of EVERY quantised
+        parameter (biases present: affine; uint8 scales without biases: ``ops.infer_quantization_mx``), else ``ValueError`` by name."""
         ops.require_gpu()
         assert precision in (3, 4)
         assert kv_dtype in ops.KV_DTYPES
@@ -107,7 +109,16 @@ class WhisperEngine:
         dev = self.device
         quantized = dict(quantized or {})
         qcfg = {k: v for k, v in (quantization or {}).items() if k in ("group_size", "bits")}
-        qfmt = {p: ops.infer_quantization(t[0].shape[1], t[1].shape[1], **qcfg) for p, t in quantized.items()}
+        qmode = (quantization or {}).get("mode")   # None: the shapes decide alone; "affine" beside uint8 scales without biases is a contradiction too
+
+        def packq(q, s, b, bias):   # (weight, scales, biases) -> the device image; biases None: a block-scaled floating-point parameter (uint8 scales)
+            return ops.pack_quantized_mx(q, s, bias, dev, mode=qmode) if b is None else ops.pack_quantized(q, s, b, bias, dev, **qcfg)
+
+        for p, t in quantized.items():
+            if t[2] is not None and qmode not in (None, "affine"):
+                raise ValueError(f"quantization mode {qmode!r} contradicts the shapes: {p} has .biases beside its .scales, which is the affine mode")
+        qfmt = {p: ops.infer_quantization_mx(t[0].shape[1], t[1].shape[1], mode=qmode) if t[2] is None else
+                ops.infer_quantization(t[0].shape[1], t[1].shape[1], **qcfg) for p, t in quantized.items()}
         # the parameters that stay packed: decoder linears off the 1500-row products; q | k | v only as a whole, in one format
         packed = {p for p in quantized if p == "decoder.token_embedding" or (p.startswith("decoder.blocks.") and p.rsplit(".", 1)[1] in ("out", "mlp1", "mlp2"))
                   or p.endswith(".cross_attn.query")}
@@ -117,7 +128,7 @@ class WhisperEngine:
                 packed.update(qkv)
         weights = dict(weights)
         for p in quantized.keys() - packed:   # dequantised once, here; rounded to fp16 with every other weight below
-            weights[p + ".weight"] = ops.dequantize_affine(ops.pack_quantized(*quantized[p], None, dev, **qcfg)).cpu()
+            weights[p + ".weight"] = ops.dequantize_packed(packq(*quantized[p], None)).cpu()
         self.quantized_decoder = bool(packed)
         w = {k: v.detach().to(torch.float16).to(torch.float32).cpu() for k, v in weights.items()}  # checkpoint dtype: fp16
 
@@ -125,8 +136,9 @@ class WhisperEngine:
             """One Linear over the concatenated rows of the parameters ``names``."""
             names = [names] if isinstance(names, str) else names
             if names[0] in packed:
-                q, s, b = (torch.cat([quantized[p][j].view(torch.int32) if j == 0 else quantized[p][j] for p in names]) for j in range(3))
-                return _Lin(None, None, ops.pack_quantized(q, s, b, bias, dev, **qcfg))
+                q, s = (torch.cat([quantized[p][j].view(torch.int32) if j == 0 else quantized[p][j] for p in names]) for j in range(2))
+                b = None if quantized[names[0]][2] is None else torch.cat([quantized[p][2] for p in names])
+                return _Lin(None, None, packq(q, s, b, bias))
             wt = torch.cat([w[p + ".weight"] for p in names])
             return _Lin(ops.pack_conv(wt, bias, dev, f16=True), ops.pack_rowmajor16(wt, bias, dev, f16=True))
 
@@ -343,7 +355,7 @@ class WhisperEngine:
         nt, H, dh = d.n_text_state, d.n_text_head, self.dh
         x = self._f(B, n, nt)
         if self.tok_emb is None:   # packed table: the rows the tokens name, dequantised, plus the positional rows
-            ops.dequantize_affine(self.logits_lin.ql, tokens, out=x.view(B * n, nt), add=self.pos_emb[off:off + n])
+            ops.dequantize_packed(self.logits_lin.ql, tokens, out=x.view(B * n, nt), add=self.pos_emb[off:off + n])
         else:
             ops.gather_rows(self.tok_emb, tokens, x, pos_table=self.pos_emb[off:off + n])
         if n == 1 and B <= 64 and self.native_decode and cross_hook is None:  # the whole 12-layer step from the native runner: one call instead of ~100 launches from Python

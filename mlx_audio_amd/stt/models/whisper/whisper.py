@@ -18,7 +18,7 @@ has no host implementation, so a ``Model`` without an engine raises ``NotImpleme
 Deliberately not carried over (host front/back ends): resampling of non-16 kHz files and streaming (AlignAtt), which raises
 ``NotImplementedError``.
 ``detect_language`` returns the reference's (language tokens, probability dicts) pair.
-Quantised checkpoints (MLX affine `-4bit` / `-8bit`, whisper.py:671-688) load: see ``load_weights``.  Other quantisation modes are not built.
+Quantised checkpoints (MLX affine `-4bit` / `-8bit`, whisper.py:671-688) and the block-scaled `-mxfp4` / `-nvfp4` / `-mxfp8` ones load: see ``load_weights``.
 """
 from __future__ import annotations
 
@@ -166,14 +166,18 @@ class Model:
         reference's predicate (whisper.py:671-688), Linear and Embedding alike and per parameter, so partly quantised checkpoints load.  Bits and
         group size follow from the shapes (``ops.infer_quantization``; ``quantization`` = the checkpoint's {"group_size", "bits"} where given).  The
         decoder's linears then run on the packed codes (``ops.qlinear``); the encoder's and the cross key / value projections are dequantised
-        once, here, and rounded to fp16 into the usual images (engine.py).  A checkpoint without ``.scales`` takes exactly the float path."""
+        once, here, and rounded to fp16 into the usual images (engine.py).  A checkpoint without ``.scales`` takes exactly the float path.
+        ``name.scales`` of uint8 without ``name.biases`` is a `-mxfp4` / `-nvfp4` / `-mxfp8` parameter (``ops.infer_quantization_mx``: the shapes name
+        the mode, and ``quantization["mode"]`` must agree); it takes the same two roads on ``mi355_qlinear_mx`` / ``mi355_dequantize_mx``.  Its
+        dequantised values are fp16-exact while the scale lies in fp16's range; outside it the same rounding to fp16 applies."""
         from .engine import WhisperEngine
 
         w = dict(weights)
         quantized = {k[:-7]: None for k in w if k.endswith(".scales")}
         try:
             for p in quantized:
-                quantized[p] = (w.pop(p + ".weight"), w.pop(p + ".scales"), w.pop(p + ".biases"))
+                wq, sc = w.pop(p + ".weight"), w.pop(p + ".scales")
+                quantized[p] = (wq, sc, w.pop(p + ".biases", None) if sc.dtype == torch.uint8 else w.pop(p + ".biases"))
             # the K / V caches live in the checkpoint's floating dtype like the reference's (whisper.py:360-361): fp16 -> fp16, bf16 -> bf16, fp32 -> fp32
             fdt = [v.dtype for v in w.values() if v.is_floating_point()]
             kv_dtype = max(set(fdt), key=fdt.count) if fdt else torch.float16

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import glob
 import importlib
+import inspect
 import json
 import logging
 import re
@@ -112,7 +113,11 @@ def base_load_model(model_path: Union[str, Path], category: str, model_remapping
     if hasattr(model, "sanitize"):
         weights = model.sanitize(weights)
     model.model_path = str(model_path)
-    model.load_weights(list(weights.items()), strict=strict)
+    quant = config.get("quantization") or config.get("quantization_config")
+    if quant is not None and "quantization" in inspect.signature(model.load_weights).parameters:
+        model.load_weights(list(weights.items()), strict=strict, quantization=quant)   # the config's mode / bits / group size must agree with the shapes
+    else:
+        model.load_weights(list(weights.items()), strict=strict)
     model.eval()
     if hasattr(arch.Model, "post_load_hook"):
         model = arch.Model.post_load_hook(model, model_path)
