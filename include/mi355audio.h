@@ -1962,6 +1962,42 @@ typedef struct {
 } mi355_dequantize_mx_args;
 int mi355_dequantize_mx(const mi355_dequantize_mx_args* a, void* stream);
 
+/* SwitchGLU on MLX's block-scaled floating-point expert weights (QuantizedSwitchLinear with mode = mxfp4 / nvfp4 / mxfp8 of the `-mxfp4` /
+ * `-nvfp4` / `-mxfp8` Ling / Ming checkpoints; moe_quant_mx.hip).  Added to ABI 37 (a new struct and a new function only).  It runs behind the
+ * same mi355_moe_plan, workspace, tile list and combine as mi355_moe_glu / mi355_moe_qglu; only the two tile launches differ.  Per projection:
+ * q uint32 [E, Ncols, Kdim bits / 32] and scales uint8 [E, Ncols, Kdim / g] in the format stated at mi355_qlinear_mx (one MI355_QMODE_* value
+ * names element, scale byte, bits and g), a float32 bias [E, Ncols] (nullable).  Per tile (at most MI355_MOE_TILE_ROWS sorted rows r of one
+ * expert e):
+ *   out[r, n] = sum_k x[r, k] * value(code[e, n, k]) * value(scale[e, n, k / g]) + bias[e, n]
+ * in fp32 and a fixed order: the arithmetic of mi355_qlinear_mx's tile form.  The codes go from HBM into registers and become exact fp16 A
+ * operands of v_mfma_f32_16x16x32_f16 (no dequantised float in memory, no LDS hop); the tile's rows are gathered through perm, split once per
+ * workgroup into fp16 hi + lo images (the limits of mi355_qlinear's tile form) and staged in LDS in element order, 256 K values at a time; two
+ * products per step (x hi, x lo).  mxfp4 / mxfp8: per 32-code step the two MFMAs fill a zeroed tile and acc = fmaf(2^e, tile, acc) (exact, a
+ * power of two).  nvfp4: the E4M3 scale of each 16-code group is multiplied into the fp16 operand (exact) and the MFMAs accumulate directly; a
+ * last half step (Kdim % 32 == 16) contributes zeros for its missing codes.  A workgroup is 32 output columns of one tile: wave (c, p) owns
+ * columns [16 c, 16 c + 16) and the runs p, p + 2, ... of 128 codes; the two K parts are joined through LDS, part 0 + part 1.  The grid is
+ * max_tiles x ceil(columns / MI355_MOE_QCOL_TILE); a tile of one row and a tile of 32 rows run the same kernel.
+ * mode 0, three launches: h = silu(gate + b_gate) * (up + b_up) in sorted order (the gate and up streams share one staged x); y = h @ down +
+ * b_down scattered through perm; the combine of mi355_moe_glu.  mode 1, one launch: out[t k + slot] = x[t] @ gate[e]^T + b_gate[e] with the gate
+ * image as [E, Ncols = I, Kdim = D]; up, down, weights, shared and res are ignored.
+ * A qmode other than the three, gate and up in different qmodes (down may differ), Kdim % 32 != 0 (16 at nvfp4; Kdim is D for gate / up, I for
+ * down) and E > MI355_MOE_MAX_EXPERTS are MI355_ERR_UNSUPPORTED with the value named; an unknown mode, null pointers, q not 16-byte aligned, D or
+ * I not a multiple of 4, the row rules of mi355_moe_glu or a short workspace are MI355_ERR_ARG.  A refused call launches nothing and leaves every
+ * output untouched.  No floating-point atomics, no persistent loops; a token's output does not depend on which other tokens share the call, and
+ * two calls on the same bytes give the same bits. */
+typedef struct {
+  const float* x; int64_t ldx; int32_t N; int32_t k; int32_t E; int32_t D; int32_t I;
+  const uint32_t* q_gate; const uint8_t* s_gate; int32_t qmode_gate;
+  const uint32_t* q_up; const uint8_t* s_up; int32_t qmode_up;
+  const uint32_t* q_down; const uint8_t* s_down; int32_t qmode_down;
+  const float* b_gate; const float* b_up; const float* b_down;
+  const float* weights;
+  const float* shared; int64_t ld_shared; const float* res; int64_t ld_res;
+  float* out; int64_t ldo;
+  void* workspace; int64_t workspace_bytes; int32_t mode;
+} mi355_moe_qglu_mx_args;
+int mi355_moe_qglu_mx(const mi355_moe_qglu_mx_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,13 +20,14 @@ LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmi355audio.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "mi355audio.h")
 SOURCES = ["api.cpp", "conv_gemm.hip", "conv_ws4.hip", "conv_ws4_p4.hip", "conv_ws4_p13.hip", "conv_ws4_p5.hip", "conv_ws4_p6.hip", "conv_ws4_p5_probe.hip", "conv_ws4_fq.hip", "upsample_poly.hip", "conv_quant.hip", "norm.hip", "group_norm.hip", "s3.hip", "conformer.hip", "narrow_attn.hip", "mid_attn.hip", "align.hip", "lstm.hip", "lstm_seq.hip", "gru.hip", "dfn.hip", "bandsplit.hip", "sanm.hip", "mossformer.hip", "attention.hip", "glue.hip", "source.hip", "fft.hip", "flash_attn.hip",
-           "decode_rules.hip", "gemv.hip", "gemv_mfma.hip", "gemv_mfma_fp8.hip", "gemm_rows.hip", "rows_pipe.hip", "transformer.hip", "rvq.hip", "ecapa.hip", "sampler.hip", "stack_step.cpp", "firered.hip", "granite_nar.hip", "moe.hip", "qlinear.hip", "moe_quant.hip", "qlinear_mx.hip"]
+           "decode_rules.hip", "gemv.hip", "gemv_mfma.hip", "gemv_mfma_fp8.hip", "gemm_rows.hip", "rows_pipe.hip", "transformer.hip", "rvq.hip", "ecapa.hip", "sampler.hip", "stack_step.cpp", "firered.hip", "granite_nar.hip", "moe.hip", "qlinear.hip", "moe_quant.hip", "qlinear_mx.hip", "moe_quant_mx.hip"]
 # per-file extra flags: source.hip and dfn.hip mirror the reference's fp32 op order one rounding at a time
 EXTRA_FLAGS = {"source.hip": ["-ffp-contract=off"], "dfn.hip": ["-ffp-contract=off"],
                # no packed fp32 instructions at all in this file (the failure COMMON_FLAGS describes, shut out at the instruction selector)
                "qlinear.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "moe_quant.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # the same per-group fold as qlinear.hip
-               "qlinear_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "qlinear_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "moe_quant_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}   # the same per-step fold as qlinear_mx.hip
 # Every translation unit: no SLP vectorisation.  Under plain -O3 hipcc packs adjacent scalar fp32 adds / multiplies into v_pk_add_f32 / v_pk_mul_f32 /
 # v_pk_fma_f32 with SGPR-pair operands; in the interior epilogue of conv_ws4_kernel that packed code produced RANDOM errors in the fused
 # instance-norm statistics (the M2 term of a few 32-column fragments per launch, different ones every run; identical inputs, stored outputs

@@ -5,13 +5,18 @@ device: the router's ``gate_proj`` and the shared experts run on the existing ``
 Quantised checkpoints (MLX's affine `-4bit` / `-8bit`, group 32 / 64 / 128) load as they are: ``sanitize`` stacks the per-expert ``weight`` /
 ``scales`` / ``biases``, the routed experts run on the packed codes (csrc/moe_quant.hip: ``ops.PackedQuantizedExperts``), and every dense parameter
 that carries ``.scales`` -- attention, shared experts, dense MLPs, the router's ``gate_proj`` (8 bits in real checkpoints), ``lm_head`` and the
-embedding -- runs on ``ops.qlinear`` / ``ops.dequantize_affine``.  Bits and group size come from the config's ``quantization`` dict (with
+embedding -- runs on ``ops.qlinear`` / ``ops.dequantize_packed``.  Bits and group size come from the config's ``quantization`` dict (with
 per-path overrides) or, without one, from the shapes.
+
+So do the `-mxfp4` / `-nvfp4` / `-mxfp8` checkpoints.  A parameter whose ``.scales`` is uint8 with no ``.biases`` beside it is an MX parameter and its
+shapes name the mode (``ops.infer_quantization_mx``); a ``mode`` in the config (global or per path) must agree.  The routed experts run on
+csrc/moe_quant_mx.hip (``ops.PackedQuantizedExpertsMX``), the dense parameters on ``ops.QuantizedLinearMX``.  Each parameter is decided on its own,
+so a checkpoint may mix the kinds (a router kept at affine 8 bits).
 
 Parameter names and ``ModelArgs`` fields are the reference's.  ``BailingMoeModel`` / ``Model`` are a host schedule on existing kernels (``rmsnorm``,
 ``linear``, ``head_norm_rope`` / ``partial_rope``, ``flash_attention`` over a ``KVCache``, ``embed_sum``): token ids -> logits for prefill and
 one-row decode steps.  NOT built (each raises by name): quantised experts at bits 2 / 3 / 5 / 6 or in MLX's non-affine modes (``.scales`` without
-``.biases``), hub download, head widths other than 64 / 128, ``rope_scaling``."""
+``.biases`` whose ``.scales`` is not uint8), hub download, head widths other than 64 / 128, ``rope_scaling``."""
 from __future__ import annotations
 
 from dataclasses import dataclass, fields
@@ -88,12 +93,38 @@ def resolve_quantization(quantization: Optional[dict], path: str, words: int, gr
     q = quantization or {}
     own = q.get(path) or q.get("model." + path)
     src = own if isinstance(own, dict) else q
+    if src.get("mode") in ops.QMODES:   # the entry speaks of the MX parameters; an affine one beside them is read from its shapes
+        src = {}
     return ops.infer_quantization(words, groups, group_size=src.get("group_size"), bits=src.get("bits"))
+
+
+def _is_mx(t, prefix: str = "") -> bool:
+    """An MX parameter: uint8 ``.scales`` with no ``.biases`` beside it."""
+    sc = t.get(f"{prefix}scales")
+    return sc is not None and sc.dtype == torch.uint8 and t.get(f"{prefix}biases") is None
+
+
+def resolve_quantization_mx(quantization: Optional[dict], path: str, words: int, groups: int) -> str:
+    """The mode of the MX parameter at ``path``: what the shapes name; ``quantization``'s ``mode`` for that path, else its global one, must agree
+    (``ops.infer_quantization_mx`` raises ValueError, here with the parameter's name)."""
+    q = quantization or {}
+    own = q.get(path) or q.get("model." + path)
+    src = own if isinstance(own, dict) else q
+    try:
+        return ops.infer_quantization_mx(words, groups, mode=src.get("mode"))[0]
+    except ValueError as err:
+        raise ValueError(f"bailing_moe: {path}: {err}") from None
 
 
 def _check_quantized_experts(w, prefix: str, quantization):
     """What is still not built for ``{prefix}.{weight,scales,biases}``, refused by name."""
     not_built = "bailing_moe: quantised experts (QuantizedSwitchLinear) "
+    if _is_mx(w, f"{prefix}."):
+        wt = w.get(f"{prefix}.weight")
+        if wt is None or wt.dtype not in (torch.uint32, torch.int32):
+            raise NotImplementedError(not_built + f"need packed uint32 codes ({prefix}.weight is {None if wt is None else wt.dtype})")
+        resolve_quantization_mx(quantization, prefix, wt.shape[-1], w[f"{prefix}.scales"].shape[-1])
+        return
     if f"{prefix}.biases" not in w:
         raise NotImplementedError(not_built + f"in a non-affine mode are not built ({prefix}.scales has no .biases beside it)")
     wt = w.get(f"{prefix}.weight")
@@ -138,16 +169,21 @@ def _rows_of(weights, name: str, pick=None) -> Dict[str, torch.Tensor]:
 
 
 def _make_lin(t: Dict[str, torch.Tensor], device, quantization, path: str):
-    """A dense Linear from its row tensors: float -> ``make_lin``; with ``scales`` -> the packed codes for ``ops.qlinear``."""
+    """A dense Linear from its row tensors: float -> ``make_lin``; with ``scales`` -> the packed codes for ``ops.qlinear``, affine or MX."""
     if "scales" not in t:
         return make_lin(t["weight"], t.get("bias"), device)
+    if _is_mx(t):
+        mode = resolve_quantization_mx(quantization, path, t["weight"].shape[-1], t["scales"].shape[-1])
+        return ops.pack_quantized_mx(t["weight"], t["scales"], t.get("bias"), device, mode=mode)
+    if "biases" not in t:
+        raise NotImplementedError(f"bailing_moe: {path} in a non-affine mode is not built ({path}.scales is {t['scales'].dtype} with no .biases beside it)")
     bits, group = resolve_quantization(quantization, path, t["weight"].shape[-1], t["scales"].shape[-1])
     return ops.pack_quantized(t["weight"], t["scales"], t["biases"], t.get("bias"), device, group_size=group, bits=bits)
 
 
 def _linear(x: torch.Tensor, l, y: torch.Tensor, *, res: Optional[torch.Tensor] = None):
     """``linear`` on [B, L, C] views for either kind of image."""
-    if not isinstance(l, ops.QuantizedLinear):
+    if not isinstance(l, (ops.QuantizedLinear, ops.QuantizedLinearMX)):
         return linear(x, l, y, res=res)
     for b in range(x.shape[0]):
         ops.qlinear(x[b], l, y[b], res=None if res is None else res[b])
@@ -160,6 +196,12 @@ class SwitchGLU:
 
     def __init__(self, weights, prefix: str, device, quantization: Optional[dict] = None):
         g = lambda n: weights.get(f"{prefix}{n}")
+        if _is_mx(weights, f"{prefix}gate_proj."):
+            for m in ("gate_proj", "up_proj", "down_proj"):   # the config's mode, where it names one, must agree with every projection
+                resolve_quantization_mx(quantization, f"{prefix}{m}", g(f"{m}.weight").shape[-1], g(f"{m}.scales").shape[-1])
+            gud = [(g(f"{m}.weight"), g(f"{m}.scales")) for m in ("gate_proj", "up_proj", "down_proj")]
+            self.experts = ops.pack_quantized_experts_mx(*gud, device, gate_b=g("gate_proj.bias"), up_b=g("up_proj.bias"), down_b=g("down_proj.bias"))
+            return
         if g("gate_proj.scales") is not None:
             packed = []
             for m in ("gate_proj", "up_proj", "down_proj"):
@@ -307,8 +349,8 @@ class BailingMoeModel:
         cache = self.make_cache() if cache is None else cache
         x = torch.empty(B, L, self.args.hidden_size, device=self.device)
         tokens = inputs.to(device=self.device, dtype=torch.int32)
-        if isinstance(self.word_embeddings, ops.QuantizedLinear):   # the quantised table: a row gather that dequantises
-            ops.dequantize_affine(self.word_embeddings, tokens, out=x.view(B * L, -1))
+        if isinstance(self.word_embeddings, (ops.QuantizedLinear, ops.QuantizedLinearMX)):   # the quantised table: a row gather that dequantises
+            ops.dequantize_packed(self.word_embeddings, tokens, out=x.view(B * L, -1))
         else:
             ops.embed_sum(self.word_embeddings, tokens.reshape(B, L, 1), x)
         h = torch.empty_like(x)
@@ -333,7 +375,7 @@ class Model:
     def __init__(self, args: ModelArgs, weights, device="cuda:0"):
         self.args = args
         self.model = BailingMoeModel(args, weights, device)
-        if args.tie_word_embeddings and isinstance(self.model.word_embeddings, ops.QuantizedLinear):
+        if args.tie_word_embeddings and isinstance(self.model.word_embeddings, (ops.QuantizedLinear, ops.QuantizedLinearMX)):
             self.lm_head = self.model.word_embeddings   # the quantised table is also the head
         else:
             name = "model.word_embeddings" if args.tie_word_embeddings else "lm_head"
@@ -377,6 +419,34 @@ def make_moe_weights(args: ModelArgs, seed: int = 0) -> Dict[str, torch.Tensor]:
                 if args.use_bias:
                     w[f"{p}mlp.{n}.bias"] = 0.1 * torch.randn(shape[0], generator=g)
     return w
+
+
+def quantize_checkpoint_mx(weights: Dict[str, torch.Tensor], args: ModelArgs, mode: str, *, everything: bool = False, affine8=()):
+    """The float checkpoint ``weights`` (sanitized names) as a `-mxfp4` / `-nvfp4` / `-mxfp8` one in the layout of the files -- ``ops.quantize_mx`` on every
+    expert matrix and, with ``everything``, on every other matrix (the embedding included), the paths in ``affine8`` at affine 8 bits, group 64, with a power-of-two scale instead (fp16-exact); per-expert ``experts.{e}.*``
+    tensors and the router under ``gate.*``, so that ``sanitize`` has its work to do -- and the float checkpoint of the dequantised values beside it."""
+    _, bits, g = ops.QMODES[mode]
+    ck, deq = {}, {}
+    for key, v in weights.items():
+        stem, kind = key.rsplit(".", 1)
+        parts, deq[key] = {kind: v}, v
+        if stem in affine8 and kind == "weight":
+            grp = v.float().reshape(v.shape[0], -1, 64)
+            scale = torch.pow(2.0, torch.ceil(torch.log2(2 * grp.abs().amax(-1).clamp_min(2.0 ** -14) / 255)))
+            codes = torch.round(grp / scale[..., None] + 128).clamp_(0, 255).to(torch.int64)
+            deq[key] = (scale[..., None] * (codes - 128)).reshape(v.shape)
+            parts = {"weight": ops.pack_codes(codes.reshape(v.shape), 8).view(torch.int32), "scales": scale.half(), "biases": (-128 * scale).half()}
+        elif kind == "weight" and v.dim() >= 2 and (".switch_mlp." in key or everything):
+            words, scales = ops.quantize_mx(v.reshape(-1, v.shape[-1]).float(), mode)
+            deq[key] = (ops.mx_code_values(ops.unpack_codes(words, bits), mode) * ops.mx_scale_values(scales, mode).repeat_interleave(g, 1)).reshape(v.shape)
+            parts = {"weight": words.view(torch.int32).reshape(*v.shape[:-1], -1), "scales": scales.reshape(*v.shape[:-1], -1)}
+        stem = stem.replace("gate.gate_proj", "gate")
+        for k, t in parts.items():
+            if ".switch_mlp." in key:
+                ck.update({f"{stem.replace('switch_mlp.', f'experts.{e}.')}.{k}": t[e] for e in range(args.num_experts)})
+            else:
+                ck[f"{stem}.{k}"] = t
+    return ck, deq
 
 
 def _block_weights(args: ModelArgs, g: torch.Generator, prefix: str) -> Dict[str, torch.Tensor]:

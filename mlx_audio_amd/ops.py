@@ -2315,21 +2315,23 @@ def _moe_rows(t: torch.Tensor, N: int, C: int):
     return t.stride(0) if N > 1 else max(t.stride(0), C)
 
 
-def switch_glu(x: torch.Tensor, experts: "PackedExperts | PackedQuantizedExperts", ids: torch.Tensor, weights: torch.Tensor, out: torch.Tensor, *,
+def switch_glu(x: torch.Tensor, experts: "PackedExperts | PackedQuantizedExperts | PackedQuantizedExpertsMX", ids: torch.Tensor, weights: torch.Tensor, out: torch.Tensor, *,
                shared: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, ws: Optional[MoeWorkspace] = None):
     """``out[t] = sum_slot weights[t, slot] * SwitchGLU(x[t])[ids[t, slot]] + shared[t] + res[t]`` (``mi355_moe_plan`` + ``mi355_moe_glu``): the
     routed expert FFN as a grouped GEMM on the matrix pipe, ``silu(gate) * up`` then ``down``, summed in slot order.  ``x`` / ``out`` / ``shared`` /
     ``res`` [N, D] float32 row views, ``ids`` [N, k] int32, ``weights`` [N, k] float32.  ``experts``: ``PackedExperts`` (float images, moe.hip) or
-    ``PackedQuantizedExperts`` (MLX's packed 4 / 8-bit codes, moe_quant.hip: ``mi355_moe_qglu``) behind the same plan, workspace and combine."""
+    ``PackedQuantizedExperts`` (MLX's packed 4 / 8-bit codes, moe_quant.hip: ``mi355_moe_qglu``) or ``PackedQuantizedExpertsMX`` (mxfp4 / nvfp4 /
+    mxfp8 codes, moe_quant_mx.hip: ``mi355_moe_qglu_mx``) behind the same plan, workspace and combine."""
     N, D = x.shape
     k = ids.shape[1]
     assert ids.shape[0] == N and ids.device == x.device and weights.device == x.device, (ids.shape, x.shape, ids.device, x.device)
     ws = moe_plan(ids, experts.E, D, experts.I, ws=ws)
     assert experts.D == D and weights.dtype == torch.float32 and weights.is_contiguous() and tuple(weights.shape) == (N, k) and weights.is_cuda
     g, u, d = experts.gate, experts.up, experts.down
-    if isinstance(experts, PackedQuantizedExperts):
-        _lib.call_struct("mi355_moe_qglu", "mi355_moe_qglu_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=experts.E, D=D, I=experts.I,
-                         **_qproj("gate", g), **_qproj("up", u), **_qproj("down", d), weights=_ptr(weights), shared=_ptr(shared),
+    if isinstance(experts, (PackedQuantizedExperts, PackedQuantizedExpertsMX)):
+        fn, proj = ("mi355_moe_qglu_mx", _qproj_mx) if isinstance(experts, PackedQuantizedExpertsMX) else ("mi355_moe_qglu", _qproj)
+        _lib.call_struct(fn, fn + "_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=experts.E, D=D, I=experts.I,
+                         **proj("gate", g), **proj("up", u), **proj("down", d), weights=_ptr(weights), shared=_ptr(shared),
                          ld_shared=0 if shared is None else _moe_rows(shared, N, D), res=_ptr(res), ld_res=0 if res is None else _moe_rows(res, N, D),
                          out=_ptr(out), ldo=_moe_rows(out, N, D), workspace=_ptr(ws.buf), workspace_bytes=ws.nbytes, mode=0)
         return out
@@ -2344,16 +2346,17 @@ def switch_glu(x: torch.Tensor, experts: "PackedExperts | PackedQuantizedExperts
 def switch_linear(x: torch.Tensor, lin: PackedSwitchLinear, ids: torch.Tensor, out: Optional[torch.Tensor] = None, *, ws: Optional[MoeWorkspace] = None):
     """``out[t, slot] = x[t] @ w[ids[t, slot]]^T + bias[ids[t, slot]]`` -> [N, k, ncols]: one launch of the grouped-GEMM tile kernel on its own
     (``mi355_moe_glu`` mode 1), the reference's ``SwitchLinear``; with a ``PackedQuantizedSwitchLinear`` its ``QuantizedSwitchLinear`` on the packed
-    codes (``mi355_moe_qglu`` mode 1)."""
+    codes (``mi355_moe_qglu`` mode 1), with a ``PackedQuantizedSwitchLinearMX`` the same on mxfp4 / nvfp4 / mxfp8 codes (``mi355_moe_qglu_mx`` mode 1)."""
     N, D = x.shape
     k = ids.shape[1]
     assert lin.kdim == D and ids.shape[0] == N and ids.device == x.device, (ids.shape, x.shape, ids.device, x.device)
     ws = moe_plan(ids, lin.E, D, lin.ncols, ws=ws)
     out = torch.empty((N, k, lin.ncols), dtype=torch.float32, device=x.device) if out is None else out
     assert tuple(out.shape) == (N, k, lin.ncols) and out.dtype == torch.float32 and out.is_cuda and out.stride(2) == 1 and out.stride(0) == k * out.stride(1)
-    if isinstance(lin, PackedQuantizedSwitchLinear):
-        _lib.call_struct("mi355_moe_qglu", "mi355_moe_qglu_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=lin.E, D=D, I=lin.ncols,
-                         **_qproj("gate", lin), out=_ptr(out), ldo=out.stride(1), workspace=_ptr(ws.buf), workspace_bytes=ws.nbytes, mode=1)
+    if isinstance(lin, (PackedQuantizedSwitchLinear, PackedQuantizedSwitchLinearMX)):
+        fn, proj = ("mi355_moe_qglu_mx", _qproj_mx) if isinstance(lin, PackedQuantizedSwitchLinearMX) else ("mi355_moe_qglu", _qproj)
+        _lib.call_struct(fn, fn + "_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=lin.E, D=D, I=lin.ncols,
+                         **proj("gate", lin), out=_ptr(out), ldo=out.stride(1), workspace=_ptr(ws.buf), workspace_bytes=ws.nbytes, mode=1)
         return out
     _lib.call_struct("mi355_moe_glu", "mi355_moe_glu_args", _stream(), x=_ptr(x), ldx=_moe_rows(x, N, D), N=N, k=k, E=lin.E, D=D, I=lin.ncols,
                      w_gate=_ptr(lin.w), b_gate=_ptr(lin.bias), out=_ptr(out), ldo=out.stride(1), workspace=_ptr(ws.buf), workspace_bytes=ws.nbytes, mode=1)
@@ -2694,3 +2697,59 @@ def _qproj(name: str, p: PackedQuantizedSwitchLinear) -> dict:
     """The fields of ``mi355_moe_qglu_args`` that describe projection ``name``."""
     return {f"q_{name}": _ptr(p.q), f"sz_{name}": _ptr(p.sz), f"bits_{name}": p.bits, f"group_{name}": p.group_size, f"szdt_{name}": KV_DTYPES[p.sz.dtype],
             f"b_{name}": _ptr(p.bias)}
+
+
+# --------------------------------------------------------------------------------------- MX expert weights (moe_quant_mx.hip)
+@dataclass
+class PackedQuantizedSwitchLinearMX:
+    """One ``QuantizedSwitchLinear`` of a `-mxfp4` / `-nvfp4` / `-mxfp8` checkpoint on the device, the 3-D analogue of ``QuantizedLinearMX``: the
+    packed words of ``[E, ncols, kdim]`` and the scale bytes as they are in the file; ``bias`` float32 [E, ncols] or None."""
+
+    q: torch.Tensor        # int32 [E, ncols, kdim * bits / 32]
+    scales: torch.Tensor   # uint8 [E, ncols, kdim / group_size]
+    bias: Optional[torch.Tensor]
+    E: int
+    ncols: int
+    kdim: int
+    mode: str
+    bits: int
+    group_size: int
+
+
+def pack_quantized_switch_linear_mx(weight_u32: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor], device, *,
+                                    mode: Optional[str] = None) -> PackedQuantizedSwitchLinearMX:
+    """``weight_u32`` uint32 [E, out, in bits / 32], ``scales`` uint8 [E, out, in / g], ``bias`` [E, out] or None.  The last two dimensions name the
+    mode (``infer_quantization_mx``); ``mode`` (the checkpoint's ``quantization.mode``) must agree."""
+    assert weight_u32.dim() == 3 and weight_u32.dtype in (torch.uint32, torch.int32), (weight_u32.shape, weight_u32.dtype)
+    q = weight_u32.contiguous().view(torch.int32)
+    assert scales.dtype == torch.uint8 and scales.dim() == 3 and scales.shape[:2] == q.shape[:2], (q.shape, scales.shape, scales.dtype)
+    mode, bits, g = infer_quantization_mx(q.shape[2], scales.shape[2], mode=mode)
+    bd = None if bias is None else bias.detach().to(device=device, dtype=torch.float32).contiguous()
+    assert bd is None or tuple(bd.shape) == tuple(q.shape[:2])
+    return PackedQuantizedSwitchLinearMX(q.to(device), scales.contiguous().to(device), bd, q.shape[0], q.shape[1], scales.shape[2] * g, mode, bits, g)
+
+
+@dataclass
+class PackedQuantizedExpertsMX:
+    """The three MX projections of one ``SwitchGLU``: ``gate`` / ``up`` over [E, I, D] (one mode), ``down`` over [E, D, I]."""
+
+    gate: PackedQuantizedSwitchLinearMX
+    up: PackedQuantizedSwitchLinearMX
+    down: PackedQuantizedSwitchLinearMX
+
+    E = property(lambda self: self.gate.E)
+    D = property(lambda self: self.gate.kdim)
+    I = property(lambda self: self.gate.ncols)
+
+
+def pack_quantized_experts_mx(gate, up, down, device, *, gate_b=None, up_b=None, down_b=None, mode: Optional[str] = None) -> PackedQuantizedExpertsMX:
+    """``gate`` / ``up`` / ``down``: each the checkpoint's ``(weight uint32, scales uint8)`` of one stacked ``QuantizedSwitchLinear``."""
+    ex = PackedQuantizedExpertsMX(pack_quantized_switch_linear_mx(*gate, gate_b, device, mode=mode), pack_quantized_switch_linear_mx(*up, up_b, device, mode=mode),
+                                  pack_quantized_switch_linear_mx(*down, down_b, device, mode=mode))
+    assert (ex.up.E, ex.up.ncols, ex.up.kdim) == (ex.E, ex.I, ex.D) and (ex.down.E, ex.down.ncols, ex.down.kdim) == (ex.E, ex.D, ex.I)
+    return ex
+
+
+def _qproj_mx(name: str, p: PackedQuantizedSwitchLinearMX) -> dict:
+    """The fields of ``mi355_moe_qglu_mx_args`` that describe projection ``name``; a mode name outside ``QMODES`` goes down as 0 and is refused there."""
+    return {f"q_{name}": _ptr(p.q), f"s_{name}": _ptr(p.scales), f"qmode_{name}": QMODES.get(p.mode, (0,))[0], f"b_{name}": _ptr(p.bias)}
