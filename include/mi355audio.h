@@ -1998,6 +1998,53 @@ typedef struct {
 } mi355_moe_qglu_mx_args;
 int mi355_moe_qglu_mx(const mi355_moe_qglu_mx_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The gated short convolution of LFM2 (lm/models/lfm2.py: ShortConv) up to its out_proj, one launch (shortconv.hip).  Added to ABI 37 (new
+ * structs and functions only).  For a right-padded batch of B items of T rows, item b with lens[b] <= T valid rows (lens nullable: all T):
+ *   u[r, :]    = xn[r, :] @ W_in^T (+ in_bias)              W_in [3H, H]: slabs B | C | x in that order
+ *   Bx[r, c]   = u[r, c] * u[r, 2H + c]                     rows t >= lens[b] of item b count as 0
+ *   z[b]       = concat(state_in[b] ([L - 1, H]), Bx[b])    state_in null: zeros
+ *   conv[t, c] = sum_{j < L} taps[c, j] * z[b][t + j, c] (+ conv_bias[c])
+ *   y[r, c]    = u[r, H + c] * conv[r, c]                   rows t >= lens[b] are written as exact zeros
+ *   state_out[b] = z[b][lens[b] .. lens[b] + L - 2]         the last L - 1 valid rows (what is left of state_in when lens[b] < L - 1)
+ * xn is the normed input, fp32, row (b, t) at xn + b x_bstride + t ldx; w_in the row-major 16-bit image (MI355_W_BF16 / MI355_W_F16, rows ldw
+ * elements apart); taps [H, L], in_bias [3H], conv_bias [H], state_in / state_out [B, L - 1, H] dense fp32.  The [rows, 3H] projection never
+ * reaches memory.  Every sum runs in a fixed order: two calls on the same bytes give the same bits.
+ *   B T <= 8 rows  step form: a weight stream; a workgroup owns eight channels and streams the three weight rows of each, K split over eight
+ *                  lanes and four waves, the input rows staged in LDS; the thread that ends up with (B, C, x) of a (row, channel) gates, applies
+ *                  the taps over the carried state and stores
+ *   otherwise      tile form: v_mfma_f32_16x16x32 (bf16 or fp16, the image's type) on W straight from HBM and 16-bit images of the input rows in
+ *                  LDS (fp16: hi + lo; bf16: hi + lo + a third, so the product sees x whole); a workgroup is 16 or 32 rows of ONE item x 32 channels with three accumulators, the Bx tile goes through LDS in
+ *                  [row][channel] order and a block starts L - 1 rows early (at an item's start those rows are state_in)
+ * L outside 2 .. 4, H % 32 != 0 and a wdtype other than the two 16-bit ones (quantised weights) are MI355_ERR_UNSUPPORTED with the value named;
+ * state_in == state_out, null pointers, xn or w_in not 16-byte aligned, ldx % 4, x_bstride % 4, ldw % 8, ldx / ldy / ldw < H are MI355_ERR_ARG.
+ * A refused call launches nothing and leaves every output untouched.  y and the states need no alignment.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* xn; int64_t x_bstride; int32_t ldx;
+  int32_t B; int32_t T; int32_t H; int32_t L;
+  const int32_t* lens;          /* device [B], nullable */
+  const void* w_in; int32_t ldw; int32_t wdtype;
+  const float* in_bias;         /* [3H] nullable */
+  const float* taps;            /* [H, L] */
+  const float* conv_bias;       /* [H] nullable */
+  const float* state_in;        /* [B, L - 1, H] nullable */
+  float* state_out;             /* [B, L - 1, H] */
+  float* y; int64_t y_bstride; int32_t ldy;
+} mi355_shortconv_args;
+int mi355_shortconv(const mi355_shortconv_args* a, void* stream);
+
+/* What mi355_shortconv would run for `a`, decided without touching the device or dereferencing a pointer of `a`: the same validation (its
+ * error code and text on refusal, *out left alone), then the form, rows = the rows template of the step form (1, 2, 4, 8) or the row block of
+ * the tile form (16, 32), row_step = the rows a workgroup stores (tile form: rows - (L - 1)), the grid, the LDS bytes of a workgroup's staging
+ * and the input columns staged per chunk. */
+enum { MI355_SHORTCONV_STEP = 1, MI355_SHORTCONV_TILE = 2 };
+typedef struct {
+  int32_t form; int32_t rows; int32_t row_step;
+  int32_t grid_x; int32_t grid_y; int32_t grid_z; int32_t lds_bytes; int32_t chunk_k;
+} mi355_shortconv_route_info;
+int mi355_shortconv_route(const mi355_shortconv_args* a, mi355_shortconv_route_info* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,3 +159,38 @@ class BatchKVCache:
 
 def _dh(c: KVCache) -> int:
     return getattr(c, "head_dim", None) or 64
+
+
+class ConvState:
+    """The carried rows of one LFM2 ``ShortConv`` layer: the reference's ``ArraysCache(size=1)`` for this use.  Two [B, L - 1, H] buffers, because
+    ``ops.shortconv`` reads ``state`` while it writes ``next_state``; ``swap()`` after the launch makes the written one current.  ``state`` is None
+    until the first swap (the kernel then reads zeros), ``offset`` counts the rows advanced, ``lengths`` (int32 [B], device, or None) are the valid
+    rows of each item of the NEXT right-padded call -- the reference's ``cache.lengths`` branch."""
+
+    def __init__(self, n_keep: int, hidden: int, device):
+        self.n_keep, self.hidden, self.device = n_keep, hidden, torch.device(device)
+        self._bufs: List[Optional[torch.Tensor]] = [None, None]
+        self._cur = -1   # index of the current buffer, -1 before the first swap
+        self.offset = 0
+        self.lengths: Optional[torch.Tensor] = None
+
+    @property
+    def state(self) -> Optional[torch.Tensor]:
+        return None if self._cur < 0 else self._bufs[self._cur]
+
+    def next_state(self, batch: int) -> torch.Tensor:
+        i = 1 - max(self._cur, 0) if self._cur >= 0 else 0
+        if self._bufs[i] is None or self._bufs[i].shape[0] != batch:
+            self._bufs[i] = torch.empty(batch, self.n_keep, self.hidden, dtype=torch.float32, device=self.device)
+        return self._bufs[i]
+
+    def swap(self, n_rows: int = 0):
+        self._cur = 1 - self._cur if self._cur >= 0 else 0
+        self.offset += n_rows
+        self.lengths = None
+
+    def empty(self) -> bool:
+        return self._cur < 0
+
+    def reset(self):
+        self._cur, self.offset, self.lengths = -1, 0, None

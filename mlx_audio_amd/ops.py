@@ -2753,3 +2753,39 @@ def pack_quantized_experts_mx(gate, up, down, device, *, gate_b=None, up_b=None,
 def _qproj_mx(name: str, p: PackedQuantizedSwitchLinearMX) -> dict:
     """The fields of ``mi355_moe_qglu_mx_args`` that describe projection ``name``; a mode name outside ``QMODES`` goes down as 0 and is refused there."""
     return {f"q_{name}": _ptr(p.q), f"s_{name}": _ptr(p.scales), f"qmode_{name}": QMODES.get(p.mode, (0,))[0], f"b_{name}": _ptr(p.bias)}
+
+
+# --------------------------------------------------------------------------------------- LFM2's gated short conv (shortconv.hip)
+SHORTCONV_STEP, SHORTCONV_TILE = 1, 2   # mi355_shortconv_route_info.form
+
+
+def shortconv(xn: torch.Tensor, w_in: RowMajor16, taps: torch.Tensor, y: torch.Tensor, *, state_in: Optional[torch.Tensor],
+              state_out: torch.Tensor, lens: Optional[torch.Tensor] = None, in_bias: Optional[torch.Tensor] = None,
+              conv_bias: Optional[torch.Tensor] = None):
+    """``ShortConv`` of LFM2 up to its ``out_proj`` in one launch (``mi355_shortconv``): y = C * conv(concat(state_in, B * x)) with (B, C, x) =
+    split(xn @ w_in^T + in_bias, 3) and ``state_out`` = the last L - 1 valid rows of the conv's input.  ``xn`` / ``y`` [B, T, H] channels-last views,
+    ``w_in`` the row-major 16-bit image of the [3H, H] weight, ``taps`` [H, L], ``state_in`` (None: zeros) / ``state_out`` [B, L - 1, H] dense and
+    distinct, ``lens`` int32 [B] for a right-padded batch.  B T <= 8 rows run the step form (a weight stream), more the tile form (MFMA)."""
+    if not isinstance(w_in, RowMajor16):
+        raise NotImplementedError(f"shortconv: quantised weights are not built ({type(w_in).__name__}; the row-major bf16 / fp16 image is)")
+    B, T, H, xbs, ldx = _nlc(xn)
+    By, Ty, Hy, ybs, ldy = _nlc(y)
+    assert (By, Ty, Hy) == (B, T, H) and w_in.n == 3 * H and w_in.k == H, (xn.shape, y.shape, w_in.n, w_in.k)
+    assert taps.dim() == 2 and taps.shape[0] == H and taps.is_contiguous() and taps.dtype == torch.float32
+    L = taps.shape[1]
+    for s in (state_in, state_out):
+        assert s is None or (s.shape == (B, L - 1, H) and s.is_contiguous() and s.dtype == torch.float32), (None if s is None else s.shape, (B, L - 1, H))
+    assert lens is None or (lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous())
+    _lib.call_struct("mi355_shortconv", "mi355_shortconv_args", _stream(), xn=_ptr(xn), x_bstride=xbs, ldx=ldx, B=B, T=T, H=H, L=L, lens=_ptr(lens),
+                     w_in=_ptr(w_in.w), ldw=w_in.w.stride(0), wdtype=w_in.wdtype, in_bias=_ptr(in_bias), taps=_ptr(taps), conv_bias=_ptr(conv_bias),
+                     state_in=_ptr(state_in), state_out=_ptr(state_out), y=_ptr(y), y_bstride=ybs, ldy=ldy)
+    return y
+
+
+def shortconv_route(B: int, T: int, H: int, L: int, **fields) -> dict:
+    """What ``shortconv`` would run for these sizes (``mi355_shortconv_route``: form, rows, row_step, grid_x / y / z, lds_bytes, chunk_k), or its refusal
+    as ``Mi355Error``.  Needs no device: the addresses are made up (aligned, non-null) and never read.  ``fields`` overrides any struct field."""
+    kw = dict(xn=0x10000000, x_bstride=T * H, ldx=H, B=B, T=T, H=H, L=L, w_in=0x20000000, ldw=H, wdtype=W_BF16, taps=0x30000000,
+              state_in=0x40000000, state_out=0x50000000, y=0x60000000, y_bstride=T * H, ldy=H)
+    kw.update(fields)
+    return _lib.call_struct_out("mi355_shortconv_route", "mi355_shortconv_args", "mi355_shortconv_route_info", **kw)
